@@ -8,12 +8,15 @@ frame 1, packed to RGBA8 and gathered to rank 0.  The image is dealt to the N ra
 launch); RCCL all-gathers the RGBA8 bands (the only collective).  Total work is fixed as N grows
 ("scaling": "strong").
 
-    python bench.py                       # N=1, defaults finish in about a minute
+    python bench.py                       # N=1: set-up, warm-up, the timed steps, the result line
+    python bench.py --full                # ... and everything else below; finishes in about a minute
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 
-Prints ONE JSON line on rank 0 (value = whole-job Msamples/s), with the roofline of the path's kernels
-(HIP events on their own stream), a labelled FAST-mode rate (the cost of the exact fold) and the
-reference CPU baseline timed on this host.
+Prints ONE JSON line on rank 0 (value = whole-job Msamples/s, ms_per_step = one timed step).  A plain run does
+only what that figure needs.  --full adds, after the timed region: the last timed frame's parity against the
+reference, the roofline of the path's kernels (HIP events on their own stream), a labelled FAST-mode rate (the
+cost of the exact fold), the secondary configurations C5, C2 and C3, and the reference CPU baseline timed on
+this host.  --dump-outputs DIR writes what the last timed step computed (float32 .npy files).
 """
 import argparse
 import json
@@ -487,6 +490,80 @@ def small_config(rt, dev_index, stream, which, reps=5):
         ctx.close()
 
 
+DUMP_BYTES = 62_000_000   # --dump-outputs writes at most this much (all files together stay under 64 MB)
+
+
+def dump_outputs(out_dir, rgba, acc):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step, as float32 .npy files.
+    rgba.npy (rows, W, 4): the gathered RGBA8 frame, one value 0..255 per channel (row 0 = bottom); accum.npy
+    (rows, W, 4): the float4 accumulation behind it (N = 1 only: with more ranks each holds its own bands).
+    A frame too large for DUMP_BYTES is written as a fixed sample of its rows (seed 0, the same rows in both
+    files and in every run); rows.npy lists the global row of every row written."""
+    os.makedirs(out_dir, exist_ok=True)
+    H, W = rgba.shape
+    n_arrays = 1 if acc is None else 2
+    n_rows = min(H, max(1, DUMP_BYTES // (n_arrays * W * 16)))
+    rows = np.arange(H) if n_rows == H else np.sort(np.random.default_rng(0).choice(H, n_rows, replace=False))
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "rgba.npy"), np.ascontiguousarray(rgba[rows]).view(np.uint8).reshape(n_rows, W, 4).astype(np.float32))
+    if acc is not None:
+        np.save(os.path.join(out_dir, "accum.npy"), np.ascontiguousarray(acc[rows], np.float32))
+
+
+def headline_roofline(gat, W, spp, args, world, launch_info, kernel_ms, main_ms, pre_ms):
+    """--full: the roofline of the path's kernels on this rank, from the timed steps' own HIP events.
+    Returns it with the kernels' seconds per launch, the launches per step and this rank's samples per step."""
+    # Roofline of the path's kernels on this rank.  SURVEY.md 8(d): there is no dense contraction and the
+    # Cornell scene lives on chip, so the binding roof for C2/C4 is the vector ALU; the sample is priced by
+    # the REFERENCE's work (FLOPS_PER_SAMPLE), whatever the kernels prune.  The path runs as two kernels per
+    # launch (pass): camera_prepass_kernel traces the camera rays and parks the sky / light samples,
+    # pt_coherent_kernel renders every path from its first surface vertex.  achieved = flops per launch /
+    # (their mean per-launch time), each kernel timed with HIP events on the stream it runs on
+    # (rt_stats.last_prepass_ms / last_main_ms).
+    local_samples = gat.n_local * W * spp
+    passes = max(1, int(launch_info.get("passes", 1)))
+    main_s = float(np.mean(main_ms)) / 1e3 / passes if main_ms else float("nan")
+    pre_s = float(np.mean(pre_ms)) / 1e3 / passes if pre_ms else 0.0
+    k_s = main_s + pre_s
+    per_launch = local_samples / passes
+    tflops = FLOPS_PER_SAMPLE * per_launch / k_s / 1e12
+    kname = launch_info.get("kernel", "?")
+    digest = lib_digest(os.path.join(REPO, "cpu-based-ray-tracer_amd", "librt_hip.so"))
+    pmc = counter_pass(kname, W, gat.H, spp, not args.fast, world, passes, digest)
+    kernels = {kname: round(main_s * 1e3, 3)}
+    if pre_s > 0:
+        kernels["camera_prepass_kernel"] = round(pre_s * 1e3, 3)
+    roof = {"bound": "valu", "achieved": round(tflops, 3), "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(tflops / VALU_PEAK_TFLOPS, 4), "traffic": None,
+            "kernel": " + ".join(kernels), "kernel_ms": round(k_s * 1e3, 3), "kernel_ms_each": kernels,
+            "dominant_kernel": kname, "dominant_frac_of_time": round(main_s / k_s, 4),
+            "render_ms_with_finalize": round(float(np.mean(kernel_ms)), 3) if kernel_ms else None,
+            "flops_per_sample": round(FLOPS_PER_SAMPLE, 1),
+            "samples_per_launch": int(per_launch), "launches_per_step": passes,
+            "frame_chunks": int(launch_info.get("chunks", 1)), "gsamples_per_s_kernels": round(per_launch / k_s / 1e9, 4),
+            "reference_work": REF_WORK, "lib_sha256": digest, "counters": None}
+    if pmc is not None:
+        # a rocprofv3 counter pass of this build and shape (profiles/): HBM bytes per launch and the
+        # kernels' VALU issue fraction / lane utilization
+        roof["traffic"] = pmc.get("hbm_bytes_per_launch")
+        # the path kernel's measured L2 -> fabric bytes per launch over its live launch time, against HBM's 8 TB/s:
+        # an UPPER bound of its HBM use (the request-size counters count at the L2's fabric side, Infinity Cache
+        # hits included; ADVICE r04), so it is named for what it measures
+        if roof["traffic"] and main_s > 0:
+            roof["fabric_frac_of_hbm_peak"] = round(roof["traffic"] / main_s / HBM_PEAK_BYTES_PER_S, 4)
+        if pmc.get("split_rdreq_dram") is not None:
+            # the requests of those that went to DRAM (TCC_EA0_{RD,WR}REQ_DRAM), per sample
+            roof["dram_requests_per_sample"] = {"read": round(pmc["split_rdreq_dram"] / per_launch, 4),
+                                                "write": round((pmc.get("split_wrreq_dram") or 0.0) / per_launch, 4)}
+        roof["counters"] = {"file": pmc["_file"], "hbm_bytes_per_sample": pmc.get("hbm_bytes_per_sample"),
+                            "valu_issue_frac": pmc.get("valu_issue_frac"), "valu_lane_utilization": pmc.get("valu_lane_utilization"),
+                            "valu_wave_insts_per_sample": pmc.get("valu_wave_insts_per_sample"),
+                            "kernel_ms_profiled": pmc.get("kernel_ms"), "traffic_method": pmc.get("hbm_correction"),
+                            "read_bytes_per_sample": pmc.get("split_read_bytes_per_sample"),
+                            "write_bytes_per_sample": pmc.get("split_write_bytes_per_sample")}
+    return roof, k_s, passes, local_samples
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -507,10 +584,17 @@ def main():
                     help="run the N > 1 path's collectives even with one rank: init_process_group, the all-gather of "
                          "the bands and the MAX all-reduce of the time (exercises RCCL on a one-GPU box)")
     ap.add_argument("--dump-image", default=None, help="rank 0 saves the gathered RGBA8 frame (.npy, row 0 = bottom)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as float32 DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: parity of the last frame, the roofline, the FAST-mode rate, the secondary "
+                         "configurations and the CPU baseline (the --no-... switches trim it); a plain run prints the headline only")
     ap.add_argument("--no-c5", action="store_true", help="skip the secondary C5 line (configs.c5; N = 1 only)")
     ap.add_argument("--c5-spp", type=int, default=4096)
     ap.add_argument("--no-small-configs", action="store_true", help="skip the secondary C2 and C3 lines (configs.c2 / c3; N = 1 only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -613,63 +697,21 @@ def main():
     value = total_samples / elapsed / 1e6
     if args.dump_image and rank == 0:
         np.save(args.dump_image, gat.image.cpu().numpy().view(np.uint32).reshape(H, W))
+    if args.dump_outputs and rank == 0:   # the last timed step's frame, and with one rank its whole accumulation
+        dump_outputs(args.dump_outputs, gat.image.cpu().numpy().view(np.uint32).reshape(H, W),
+                     ctx.accumulation() if world == 1 else None)
+    # everything below the timed region's own figures is --full's: a plain run goes straight to the result line
     # the metric's second half: the last timed frame against the reference (outside the timed region)
-    parity = frame_parity(ctx, gat, W, H, spp, args, world, dist, torch, dev, gloo, use_dist)
-
-    # Roofline of the path's kernels on this rank.  SURVEY.md 8(d): there is no dense contraction and the
-    # Cornell scene lives on chip, so the binding roof for C2/C4 is the vector ALU; the sample is priced by
-    # the REFERENCE's work (FLOPS_PER_SAMPLE), whatever the kernels prune.  The path runs as two kernels per
-    # launch (pass): camera_prepass_kernel traces the camera rays and parks the sky / light samples,
-    # pt_coherent_kernel renders every path from its first surface vertex.  achieved = flops per launch /
-    # (their mean per-launch time), each kernel timed with HIP events on the stream it runs on
-    # (rt_stats.last_prepass_ms / last_main_ms).
-    local_samples = gat.n_local * W * spp
-    passes = max(1, int(launch_info.get("passes", 1)))
-    main_s = float(np.mean(main_ms)) / 1e3 / passes if main_ms else float("nan")
-    pre_s = float(np.mean(pre_ms)) / 1e3 / passes if pre_ms else 0.0
-    k_s = main_s + pre_s
-    per_launch = local_samples / passes
-    tflops = FLOPS_PER_SAMPLE * per_launch / k_s / 1e12
-    kname = launch_info.get("kernel", "?")
-    digest = lib_digest(os.path.join(REPO, "cpu-based-ray-tracer_amd", "librt_hip.so"))
-    pmc = counter_pass(kname, W, H, spp, not args.fast, world, passes, digest)
-    kernels = {kname: round(main_s * 1e3, 3)}
-    if pre_s > 0:
-        kernels["camera_prepass_kernel"] = round(pre_s * 1e3, 3)
-    roof = {"bound": "valu", "achieved": round(tflops, 3), "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-            "frac": round(tflops / VALU_PEAK_TFLOPS, 4), "traffic": None,
-            "kernel": " + ".join(kernels), "kernel_ms": round(k_s * 1e3, 3), "kernel_ms_each": kernels,
-            "dominant_kernel": kname, "dominant_frac_of_time": round(main_s / k_s, 4),
-            "render_ms_with_finalize": round(float(np.mean(kernel_ms)), 3) if kernel_ms else None,
-            "flops_per_sample": round(FLOPS_PER_SAMPLE, 1),
-            "samples_per_launch": int(per_launch), "launches_per_step": passes,
-            "frame_chunks": int(launch_info.get("chunks", 1)), "gsamples_per_s_kernels": round(per_launch / k_s / 1e9, 4),
-            "reference_work": REF_WORK, "lib_sha256": digest, "counters": None}
-    if pmc is not None:
-        # a rocprofv3 counter pass of this build and shape (profiles/): HBM bytes per launch and the
-        # kernels' VALU issue fraction / lane utilization
-        roof["traffic"] = pmc.get("hbm_bytes_per_launch")
-        # the path kernel's measured L2 -> fabric bytes per launch over its live launch time, against HBM's 8 TB/s:
-        # an UPPER bound of its HBM use (the request-size counters count at the L2's fabric side, Infinity Cache
-        # hits included), so it is named for what it measures
-        if roof["traffic"] and main_s > 0:
-            roof["fabric_frac_of_hbm_peak"] = round(roof["traffic"] / main_s / HBM_PEAK_BYTES_PER_S, 4)
-        if pmc.get("split_rdreq_dram") is not None:
-            # the requests of those that went to DRAM (TCC_EA0_{RD,WR}REQ_DRAM), per sample
-            roof["dram_requests_per_sample"] = {"read": round(pmc["split_rdreq_dram"] / per_launch, 4),
-                                                "write": round((pmc.get("split_wrreq_dram") or 0.0) / per_launch, 4)}
-        roof["counters"] = {"file": pmc["_file"], "hbm_bytes_per_sample": pmc.get("hbm_bytes_per_sample"),
-                            "valu_issue_frac": pmc.get("valu_issue_frac"), "valu_lane_utilization": pmc.get("valu_lane_utilization"),
-                            "valu_wave_insts_per_sample": pmc.get("valu_wave_insts_per_sample"),
-                            "kernel_ms_profiled": pmc.get("kernel_ms"), "traffic_method": pmc.get("hbm_correction"),
-                            "read_bytes_per_sample": pmc.get("split_read_bytes_per_sample"),
-                            "write_bytes_per_sample": pmc.get("split_write_bytes_per_sample")}
+    parity = frame_parity(ctx, gat, W, H, spp, args, world, dist, torch, dev, gloo, use_dist) if args.full else None
+    roof = None
+    if args.full:
+        roof, k_s, passes, local_samples = headline_roofline(gat, W, spp, args, world, launch_info, kernel_ms, main_ms, pre_ms)
 
     # labelled secondary: the FAST mode's rate on this rank (forward throughput accumulation: within RMSE 1e-5
     # of the reference, not its rounding sequence) -- what the EXACT inner-first fold (MC/Renderer.cpp:208,213)
     # costs; one render after the timed steps, kernels only
     fast = None
-    if not args.fast and not args.no_fast_probe:
+    if args.full and not args.fast and not args.no_fast_probe:
         ctx.render(cam, spp, first_frame=1, seed=0, rr=0.8, exact=False, fetch=False)
         st = ctx.stats()
         fk = (st.last_main_ms + st.last_prepass_ms) / 1e3
@@ -681,15 +723,15 @@ def main():
     ctx.close()
     ctx = None
     configs = None
-    if world == 1 and not args.no_c5:
+    if args.full and world == 1 and not args.no_c5:
         configs = {"c5": c5_config(rt, dev.index, stream, args.c5_spp, args.fast)}
-    if world == 1 and not args.no_small_configs and not args.fast:
+    if args.full and world == 1 and not args.no_small_configs and not args.fast:
         configs = configs or {}
         for which in ("c2", "c3"):
             configs[which] = small_config(rt, dev.index, stream, which)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(W, H, args.cpu_seconds)
         if cpu is not None:
             cpu["gpu_over_cpu"] = round(value / cpu["value"], 1)
@@ -702,6 +744,7 @@ def main():
             "metric": "Msamples/s Cornell box 1024spp @1/2/4/8 MI355X; per-pixel RMSE vs CPU ref",
             "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "strong",
+            "full": args.full,
             "vs_baseline": None, "dtype": "f32+f64", "data": "synthetic (reference Cornell box scene, Philox RNG seed 0)",
             "config": {"workload": f"C4 cornell {W}x{H} {spp}spp", "width": W, "height": H, "spp": spp, "rr": 0.8,
                        "seed": 0, "band_rows": args.band, "accumulation": "fast" if args.fast else "exact",

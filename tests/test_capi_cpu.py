@@ -79,19 +79,22 @@ def test_scene_from_raw_meshes_equals_reference_scene():
 
 
 def test_obj_loader_equals_reference_loader(tmp_path):
-    ref = "/root/reference/Monte Carlo Path Tracer/8599RayTracerGUI/src/cornellbox"
+    ref = os.path.join(G, "cornellbox")   # the reference's own OBJ files (MC/cornellbox), byte for byte
     meshes = O.cornell_meshes()
     s = rt.Scene()
     for (name, raw, alb, em) in meshes:
-        path = os.path.join(ref, name + ".obj")
-        if not os.path.exists(path):
-            # GPU box: no reference tree -- write the fixture positions as an OBJ (same numbers)
-            path = str(tmp_path / (name + ".obj"))
-            with open(path, "w") as f:
-                for v in raw.reshape(-1, 3):
-                    f.write("v %r %r %r\n" % tuple(float(c) for c in v))
-                for i in range(raw.shape[0]):
-                    f.write("f %d %d %d\n" % (3 * i + 1, 3 * i + 2, 3 * i + 3))
+        s.add_obj(os.path.join(ref, name + ".obj"), alb, em)
+    s.build()
+    check_scene(s)
+    # and the fixture's positions written back as an OBJ (the same numbers in another spelling)
+    s = rt.Scene()
+    for (name, raw, alb, em) in meshes:
+        path = str(tmp_path / (name + ".obj"))
+        with open(path, "w") as f:
+            for v in raw.reshape(-1, 3):
+                f.write("v %r %r %r\n" % tuple(float(c) for c in v))
+            for i in range(raw.shape[0]):
+                f.write("f %d %d %d\n" % (3 * i + 1, 3 * i + 2, 3 * i + 3))
         s.add_obj(path, alb, em)
     s.build()
     check_scene(s)

@@ -138,9 +138,7 @@ def test_render_incremental_equals_batched(scene):
 
 
 def test_obj_loader_matches_reference_positions():
-    ref = "/root/reference/Monte Carlo Path Tracer/8599RayTracerGUI/src/cornellbox"
-    if not os.path.isdir(ref):
-        pytest.skip("reference OBJ files not present (GPU box)")
+    ref = os.path.join(G, "cornellbox")   # the reference's own OBJ files (MC/cornellbox), byte for byte
     import ctypes as C
     for (name, raw, _, _) in O.cornell_meshes():
         n = O.lib().or_obj_positions(os.path.join(ref, name + ".obj").encode(), None, 0)

@@ -6,7 +6,7 @@
 #   tests                  the GPU suite (pytest -m gpu)                          -> pytest_gpu.log
 #   tests:EXPR             only the GPU tests matching -k EXPR                     -> pytest_gpu_k.log
 #   smoke                  __graft_entry__.smoke()                                -> smoke.log
-#   bench                  the default bench line (C4, N = 1)                     -> bench.log
+#   bench                  the full bench line (C4, N = 1, bench.py --full)       -> bench.log
 #   configs                C1..C5 and the denoiser (tools/bench_configs.py)       -> configs.jsonl
 #   c5full                 C5 at its full 4096 spp (warm-up at 4096 spp)                            -> c5_4096.jsonl
 #   prof                   rocprofv3 trace + PMC passes of the bench command      -> profiles via profiles/run_rocprof.sh
@@ -43,7 +43,7 @@ for step in "$@"; do
       timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
       cat "$OUT/smoke.log" ;;
     bench)
-      timeout -k 10 300 python3 bench.py > "$OUT/bench.log" 2>&1
+      timeout -k 10 300 python3 bench.py --full > "$OUT/bench.log" 2>&1
       tail -1 "$OUT/bench.log" | cut -c1-600 ;;
     configs)
       timeout -k 10 400 python3 -u tools/bench_configs.py > "$OUT/configs.jsonl" 2> "$OUT/configs.err"
