@@ -20,6 +20,8 @@ LIB_PATH = os.path.join(PKG_DIR, "librt_hip.so")
 API_VERSION = 4
 
 RT_OK = 0
+RT_ERR_INVALID = -1
+RT_ERR_STATE = -4
 RT_ERR_OVERFLOW = -6
 RENDER_EXACT = 1
 RENDER_COUNT = 2
@@ -31,7 +33,11 @@ _lib = None
 
 
 class RtError(RuntimeError):
-    pass
+    """A failed C-ABI call; `status` is its rt_status (None when the failure is the binding's own)."""
+
+    def __init__(self, msg, status=None):
+        super().__init__(msg)
+        self.status = status
 
 
 class Camera(C.Structure):
@@ -44,6 +50,20 @@ class DeviceCfg(C.Structure):
 
 class RenderParams(C.Structure):
     _fields_ = [("first_frame", C.c_uint32), ("n_frames", C.c_uint32), ("seed", C.c_uint64), ("rr", C.c_float), ("flags", C.c_uint32)]
+
+
+class NpMaterial(C.Structure):
+    """rt_np_material: a non-physical path tracer sphere's material (NP/Material.h:24-146)."""
+    _fields_ = [("kind", C.c_int32), ("albedo", C.c_float * 3), ("fuzziness", C.c_float), ("refractive_index", C.c_float)]
+
+
+class NpParams(C.Structure):
+    _fields_ = [("first_frame", C.c_uint32), ("n_frames", C.c_uint32), ("seed", C.c_uint64), ("diffuse_model", C.c_int32),
+                ("gamma", C.c_int32), ("flags", C.c_uint32)]
+
+
+NP_DIFFUSE, NP_METAL, NP_DIELECTRIC = 0, 1, 2
+KERNEL_NP = 4
 
 
 class Stats(C.Structure):
@@ -63,7 +83,7 @@ class GroupStats(C.Structure):
 _DIAGNOSTIC = {"rt_debug_counters", "rt_read_accumulation", "rt_scene_walk_orders", "rt_scene_whitted_orders",
                "rt_scene_whitted_orders_half"}   # may be absent from an older A/B build
 
-KERNEL_NAMES = {0: "pt_megakernel", 1: "pt_coherent_kernel", 2: "whitted_kernel", 3: "pt_coherent_kernel"}
+KERNEL_NAMES = {0: "pt_megakernel", 1: "pt_coherent_kernel", 2: "whitted_kernel", 3: "pt_coherent_kernel", 4: "np_kernel"}
 # rt_stats.kernel_reason (include/rt_capi.h RT_KERNEL_REASON_*)
 KERNEL_REASON_DEFAULT, KERNEL_REASON_TABLES_LDS, KERNEL_REASON_MATERIALS, KERNEL_REASON_MODE, KERNEL_REASON_KNOB = 0, 1, 2, 3, 4
 KERNEL_REASON_TRIANGLES, KERNEL_REASON_SPHERES = 5, 6
@@ -157,6 +177,12 @@ def lib():
         "rt_render_denoised": (i32, [vp, C.POINTER(Camera), fp, fp, u32, u64, C.c_float, C.POINTER(DenoiseParams), C.POINTER(u32), fp]),
         "rt_denoise_restart": (i32, [vp]),
         "rt_get_gbuffer": (i32, [vp, fp, fp, fp, C.POINTER(i32), fp]),
+        "rt_scene_add_np_sphere": (i32, [vp, fp, C.c_float, C.POINTER(NpMaterial), C.POINTER(i32)]),
+        "rt_scene_add_np_scene": (i32, [vp]),
+        "rt_scene_np_count": (i32, [vp, C.POINTER(u32)]),
+        "rt_np_params_default": (None, [C.POINTER(NpParams)]),
+        "rt_render_np": (i32, [vp, C.POINTER(Camera), C.POINTER(NpParams), C.POINTER(u32), fp]),
+        "rt_np_trace": (i32, [vp, u64, fp, fp, C.POINTER(i32), fp, C.POINTER(i32)]),
         "rt_group_create": (i32, [C.POINTER(vp), C.POINTER(i32), u32]),
         "rt_group_destroy": (None, [vp]),
         "rt_group_last_error": (C.c_char_p, [vp]),
@@ -197,7 +223,7 @@ class Scene:
     @staticmethod
     def _check(st, what):
         if st != RT_OK:
-            raise RtError(f"{what} failed with status {st}")
+            raise RtError(f"{what} failed with status {st}", st)
 
     @classmethod
     def cornell(cls, extra=()):
@@ -297,6 +323,36 @@ class Scene:
         s = cls()
         s._check(lib().rt_scene_add_two_spheres_scene(s.h), "rt_scene_add_two_spheres_scene")
         return s.build()
+
+    # ---- the non-physical path tracer's spheres (NP/Hittable.h:98-141, NP/Material.h)
+    def add_np_sphere(self, center, radius, kind, albedo=(0.5, 0.5, 0.5), fuzziness=0.0, refractive_index=1.5):
+        """Sphere(center, radius, material): kind NP_DIFFUSE / NP_METAL / NP_DIELECTRIC; the radius may be negative
+        (a hollow inside a dielectric sphere); returns the sphere's index."""
+        m = NpMaterial(int(kind), (C.c_float * 3)(*[float(a) for a in albedo]), float(fuzziness), float(refractive_index))
+        sid = C.c_int32()
+        self._check(lib().rt_scene_add_np_sphere(self.h, _fp(np.asarray(center, np.float32)), float(radius), C.byref(m), C.byref(sid)),
+                    "rt_scene_add_np_sphere")
+        return sid.value
+
+    @classmethod
+    def np_scene(cls):
+        """The non-physical path tracer's six spheres (NP/mainloop.cpp:30-40)."""
+        s = cls()
+        s._check(lib().rt_scene_add_np_scene(s.h), "rt_scene_add_np_scene")
+        return s.build()
+
+    @classmethod
+    def np_spheres(cls, spheres):
+        """A built scene of (center, radius, kind, albedo, fuzziness, refractive_index) tuples, in that order."""
+        s = cls()
+        for (center, radius, kind, albedo, fuzziness, refractive_index) in spheres:
+            s.add_np_sphere(center, radius, kind, albedo=albedo, fuzziness=fuzziness, refractive_index=refractive_index)
+        return s.build()
+
+    def np_count(self):
+        n = C.c_uint32()
+        self._check(lib().rt_scene_np_count(self.h, C.byref(n)), "rt_scene_np_count")
+        return n.value
 
     def build(self):
         self._check(lib().rt_scene_build(self.h), "rt_scene_build")
@@ -541,7 +597,7 @@ class Context:
     def _check(self, st, what):
         if st != RT_OK:
             msg = lib().rt_last_error(self.h)
-            raise RtError(f"{what} failed ({st}): {msg.decode() if msg else ''}")
+            raise RtError(f"{what} failed ({st}): {msg.decode() if msg else ''}", st)
 
     def upload(self, scene):
         self._check(lib().rt_upload_scene(self.h, scene.h), "rt_upload_scene")
@@ -576,6 +632,26 @@ class Context:
             return rgba, acc
         self._check(lib().rt_render(self.h, C.byref(cam), C.byref(p), None, None), "rt_render")
         return None
+
+    def render_np(self, cam, n_frames, first_frame=1, seed=0, diffuse_model=1, gamma=1, exact=True, fetch=True):
+        """rt_render_np: n_frames frames of the non-physical path tracer; (rgba, accum) of the local rows when fetch."""
+        p = NpParams(first_frame, n_frames, seed, diffuse_model, gamma, RENDER_EXACT if exact else 0)
+        if fetch:
+            rgba = np.zeros((self.local_rows, self.W), np.uint32)
+            acc = np.zeros((self.local_rows, self.W, 4), np.float32)
+            self._check(lib().rt_render_np(self.h, C.byref(cam), C.byref(p), rgba.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(acc)), "rt_render_np")
+            return rgba, acc
+        self._check(lib().rt_render_np(self.h, C.byref(cam), C.byref(p), None, None), "rt_render_np")
+        return None
+
+    def np_trace(self, org, dirs):
+        """rt_np_trace: (sphere index or -1, t, front-face flag) of the closest hit of every ray."""
+        org = np.ascontiguousarray(org, np.float32); dirs = np.ascontiguousarray(dirs, np.float32)
+        n = org.shape[0]
+        sph = np.zeros(n, np.int32); t = np.zeros(n, np.float32); front = np.zeros(n, np.int32)
+        self._check(lib().rt_np_trace(self.h, n, _fp(org), _fp(dirs), sph.ctypes.data_as(C.POINTER(C.c_int32)), _fp(t),
+                                      front.ctypes.data_as(C.POINTER(C.c_int32))), "rt_np_trace")
+        return sph, t, front
 
     def reset_accumulation(self):
         """Renderer::Reaccumulate (MC/Renderer.h:57-60): zero the accumulation buffer."""

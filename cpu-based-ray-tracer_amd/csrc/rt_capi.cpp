@@ -14,6 +14,7 @@
 
 #include "rt_kernels.h"
 #include "rt_knobs.h"
+#include "rt_np.h"
 #include "rt_scene.h"
 
 struct rt_scene {
@@ -50,6 +51,7 @@ struct rt_ctx {
     bool bvh_prepass = true;     // split scenes: the BVH variant's paths start from the camera pre-pass (RT_BVH_PREPASS=0: off)
     bool pre_defer_walk = true;  // ... whose camera rays into the walked subtree are traced by the path kernel (RT_PRE_DEFER=0: walked there)
     float4 *d_wmats = nullptr, *d_plights = nullptr, *d_went = nullptr, *d_wtris = nullptr;
+    float4* d_np = nullptr;       // non-physical path tracer spheres (FlatScene::npsph)
     rt_scene_header hdr{};
     bool has_scene = false;
     // image
@@ -235,6 +237,7 @@ void rt_scene_destroy(rt_scene* s) { delete s; }
 rt_status rt_scene_add_cornell_box(rt_scene* s)
 {
     if (!s) return RT_ERR_INVALID;
+    if (s->builder.num_np()) return RT_ERR_INVALID;   // an NP scene holds nothing else
     s->builder.add_cornell_box();
     s->built = false;
     return RT_OK;
@@ -243,6 +246,7 @@ rt_status rt_scene_add_cornell_box(rt_scene* s)
 rt_status rt_scene_add_mesh(rt_scene* s, const float* raw, uint64_t n_tris, const float albedo[3], const float emission[3], int32_t* mesh_id)
 {
     if (!s || (!raw && n_tris) || !albedo || !emission || n_tris == 0) return RT_ERR_INVALID;
+    if (s->builder.num_np()) return RT_ERR_INVALID;   // an NP scene holds nothing else
     rt::MeshDesc m;
     m.raw.assign(raw, raw + 9 * n_tris);
     m.material = rt::MaterialDesc{{albedo[0], albedo[1], albedo[2]}, {emission[0], emission[1], emission[2]}};
@@ -257,6 +261,7 @@ rt_status rt_scene_add_sphere(rt_scene* s, const float center[3], float radius, 
                               int32_t* entity_id)
 {
     if (!s || !center || !albedo || !emission || !(radius > 0.0f) || !std::isfinite(radius)) return RT_ERR_INVALID;
+    if (s->builder.num_np()) return RT_ERR_INVALID;   // an NP scene holds nothing else
     const int id = s->builder.add_sphere(rt::F3{center[0], center[1], center[2]}, radius,
                                          rt::MaterialDesc{{albedo[0], albedo[1], albedo[2]}, {emission[0], emission[1], emission[2]}});
     if (entity_id) *entity_id = id;
@@ -388,8 +393,43 @@ rt_status rt_scene_add_world_mesh(rt_scene* s, const float* vertices, uint32_t n
 rt_status rt_scene_add_two_spheres_scene(rt_scene* s)
 {
     if (!s) return RT_ERR_INVALID;
+    if (s->builder.num_np()) return RT_ERR_INVALID;   // an NP scene holds nothing else
     s->builder.add_two_spheres_scene();
     s->built = false;
+    return RT_OK;
+}
+
+// ---- the non-physical path tracer's scene (NP/Hittable.h, NP/Material.h, NP/mainloop.cpp:30-40)
+rt_status rt_scene_add_np_sphere(rt_scene* s, const float center[3], float radius, const rt_np_material* m, int32_t* id)
+{
+    if (!s || !center || !m) return RT_ERR_INVALID;
+    if (m->kind < RT_NP_DIFFUSE || m->kind > RT_NP_DIELECTRIC) return RT_ERR_INVALID;
+    const float v[9] = {center[0], center[1], center[2], radius, m->albedo[0], m->albedo[1], m->albedo[2], m->fuzziness, m->refractive_index};
+    for (float x : v) if (!std::isfinite(x)) return RT_ERR_INVALID;
+    if (radius == 0.0f || !(m->refractive_index > 0.0f)) return RT_ERR_INVALID;
+    if (s->builder.has_other_than_np()) return RT_ERR_INVALID;   // an NP scene holds nothing else
+    rt::NpSphere sp;
+    sp.center = rt::F3{center[0], center[1], center[2]}; sp.radius = radius; sp.kind = m->kind;
+    sp.albedo = rt::F3{m->albedo[0], m->albedo[1], m->albedo[2]};
+    sp.fuzziness = m->fuzziness; sp.refractive_index = m->refractive_index;
+    const int k = s->builder.add_np_sphere(sp);
+    if (id) *id = k;
+    s->built = false;
+    return RT_OK;
+}
+
+rt_status rt_scene_add_np_scene(rt_scene* s)
+{
+    if (!s || s->builder.has_other_than_np()) return RT_ERR_INVALID;
+    s->builder.add_np_scene();
+    s->built = false;
+    return RT_OK;
+}
+
+rt_status rt_scene_np_count(const rt_scene* s, uint32_t* n)
+{
+    if (!s || !n) return RT_ERR_INVALID;
+    *n = (uint32_t)s->builder.num_np();
     return RT_OK;
 }
 
@@ -406,6 +446,7 @@ rt_status rt_scene_get_info(const rt_scene* s, rt_scene_info* info)
 {
     if (!s || !info || !s->built) return s && !s->built ? RT_ERR_STATE : RT_ERR_INVALID;
     const auto& h = s->flat.hdr;
+    if (h.n_np > 0) { *info = rt_scene_info{}; return RT_OK; }   // an NP scene has no meshes, tree or lights
     info->n_meshes = h.n_mats;
     info->n_tris = h.n_tris;
     info->n_nodes = h.n_nodes;
@@ -561,7 +602,7 @@ void rt_destroy(rt_ctx* c)
     dfree(c->d_sboxes); dfree(c->d_stri); dfree(c->d_wcopies); dfree(c->d_worders);
     dfree(c->d_nodes); dfree(c->d_tris); dfree(c->d_mats); dfree(c->d_lnodes); dfree(c->d_ltris); dfree(c->d_lboxes); dfree(c->d_wmats); dfree(c->d_plights);
     dfree(c->d_tabc);
-    dfree(c->d_went); dfree(c->d_wtris);
+    dfree(c->d_went); dfree(c->d_wtris); dfree(c->d_np);
     dfree(c->d_gb_color); dfree(c->d_gb_pos); dfree(c->d_gb_nrm); dfree(c->d_spatial); dfree(c->d_temporal); dfree(c->d_prev_color);
     dfree(c->d_gb_prim); dfree(c->d_prev_prim); dfree(c->d_dn_rgba); dfree(c->d_lbuf); dfree(c->d_sky);
     dfree(c->d_crec); dfree(c->d_seg_list); dfree(c->d_tile_boxes);
@@ -616,6 +657,7 @@ rt_status rt_upload_scene(rt_ctx* c, const rt_scene* s)
     if ((r = upload(c, c->d_plights, s->flat.plights)) != RT_OK) return r;
     if ((r = upload(c, c->d_went, s->flat.went)) != RT_OK) return r;
     if ((r = upload(c, c->d_wtris, s->flat.wtris)) != RT_OK) return r;
+    if ((r = upload(c, c->d_np, s->flat.npsph)) != RT_OK) return r;
     c->hdr = s->flat.hdr;
     c->has_scene = true;
     return RT_OK;
@@ -733,6 +775,7 @@ rt_status rt_render(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, 
     if (!c || !cam || !p) return RT_ERR_INVALID;
     if (!c->has_scene) { c->err = "no scene uploaded"; return RT_ERR_STATE; }
     if (!c->d_accum) { c->err = "no viewport (rt_resize)"; return RT_ERR_STATE; }
+    if (c->hdr.n_np > 0) { c->err = "a non-physical path tracer scene renders with rt_render_np"; return RT_ERR_STATE; }
     if (c->hdr.n_went > 0 && !(p->flags & RT_RENDER_WHITTED)) { c->err = "a Whitted world renders with RT_RENDER_WHITTED"; return RT_ERR_INVALID; }
     if (p->first_frame == 0) { c->err = "first_frame is 1-based"; return RT_ERR_INVALID; }
     // a survival probability >= 1 never terminates a path in a closed scene (the reference recurses
@@ -1107,6 +1150,100 @@ rt_status rt_render(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, 
     return RT_OK;
 }
 
+// ------------------------------------------------------------------ the non-physical path tracer (rt_np.hip)
+void rt_np_params_default(rt_np_params* p)
+{
+    if (!p) return;
+    // NP/NPPTToolbox.h:34-44: ON_Sphere, gamma 1
+    *p = rt_np_params{1u, 1u, 0ull, 1, 1, RT_RENDER_EXACT};
+}
+
+rt_status rt_render_np(rt_ctx* c, const rt_camera* cam, const rt_np_params* p, uint32_t* out_rgba, float* out_accum)
+{
+    if (!c || !cam || !p) return RT_ERR_INVALID;
+    if (!c->has_scene) { c->err = "no scene uploaded"; return RT_ERR_STATE; }
+    if (c->hdr.n_np == 0) { c->err = "rt_render_np renders a scene of rt_scene_add_np_sphere spheres"; return RT_ERR_STATE; }
+    if (!c->d_accum) { c->err = "no viewport (rt_resize)"; return RT_ERR_STATE; }
+    if (p->first_frame == 0) { c->err = "first_frame is 1-based"; return RT_ERR_INVALID; }
+    if (p->diffuse_model < 0 || p->diffuse_model > 2) { c->err = "diffuse_model is 0, 1 or 2"; return RT_ERR_INVALID; }
+    if (p->gamma < 1) { c->err = "gamma must be >= 1"; return RT_ERR_INVALID; }
+    if (p->flags & ~RT_RENDER_EXACT) { c->err = "rt_render_np takes RT_RENDER_EXACT or 0"; return RT_ERR_INVALID; }
+    HIPC(c, hipSetDevice(c->device));
+    const bool exact = (p->flags & RT_RENDER_EXACT) != 0;
+    NpParams P{};
+    P.spheres = c->d_np; P.n_spheres = c->hdr.n_np;
+    std::memcpy(P.cam_pos, cam->position, sizeof P.cam_pos);
+    std::memcpy(P.iproj, cam->inv_projection, sizeof P.iproj);
+    std::memcpy(P.iview, cam->inv_view, sizeof P.iview);
+    P.W = c->W; P.H = c->H;
+    P.first_frame = p->first_frame; P.n_frames = p->n_frames;
+    P.seed = p->seed;
+    P.diffuse_model = p->diffuse_model; P.gamma = p->gamma;
+    P.band = c->band; P.rank = c->rank; P.nranks = c->nranks; P.n_local_rows = c->local_rows;
+    P.tiles_x = (c->W + 7) / 8;
+    P.accum = c->d_accum; P.rgba = c->d_rgba;
+    c->last_flags = p->flags;
+    // the work counters of rt_get_stats read 0 for this kernel
+    HIPC(c, hipMemsetAsync(c->d_counters, 0, 13 * 8, c->stream));
+    c->kev_used = 0;
+    c->kev_prepass = false;
+    if (p->n_frames > 0 && c->local_rows > 0) {
+        while (c->kev.size() < 3) {
+            hipEvent_t e;
+            HIPC(c, hipEventCreate(&e));
+            c->kev.push_back(e);
+        }
+        uint32_t grid = 0;
+        HIPC(c, hipEventRecord(c->ev0, c->stream));
+        HIPC(c, hipEventRecord(c->kev[0], c->stream));
+        HIPC(c, hipEventRecord(c->kev[1], c->stream));
+        HIPC(c, rt_launch_np(P, exact, c->stream, &grid));
+        HIPC(c, hipEventRecord(c->kev[2], c->stream));
+        HIPC(c, hipEventRecord(c->ev1, c->stream));
+        c->kev_used = 1;
+        c->stats.grid = grid;
+        c->stats.n_chunks = 1; c->stats.n_passes = 1;
+        c->stats.kernel = RT_KERNEL_NP;
+        c->stats.kernel_reason = RT_KERNEL_REASON_DEFAULT;
+        c->pending_stats = true;
+    }
+    c->stats.samples = (uint64_t)c->local_rows * c->W * p->n_frames;
+    if (out_rgba || out_accum) {
+        const size_t npx = (size_t)c->local_rows * c->W;
+        if (out_rgba) HIPC(c, hipMemcpyAsync(out_rgba, c->d_rgba, npx * 4, hipMemcpyDeviceToHost, c->stream));
+        if (out_accum) HIPC(c, hipMemcpyAsync(out_accum, c->d_accum, npx * 16, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipStreamSynchronize(c->stream));
+        return check_overflow(c);
+    }
+    return RT_OK;
+}
+
+rt_status rt_np_trace(rt_ctx* c, uint64_t n, const float* org, const float* dir, int32_t* sphere, float* t, int32_t* front)
+{
+    if (!c || (n && (!org || !dir || !sphere || !t || !front))) return RT_ERR_INVALID;
+    if (!c->has_scene || c->hdr.n_np == 0) { c->err = "no non-physical path tracer scene uploaded"; return RT_ERR_STATE; }
+    if (n == 0) return RT_OK;
+    if (n > 0x7FFFFFFFull / 3) return RT_ERR_INVALID;   // the kernel indexes 3 floats per ray in 32 bits
+    HIPC(c, hipSetDevice(c->device));
+    float *d_o = nullptr, *d_d = nullptr, *d_t = nullptr; int32_t *d_s = nullptr, *d_f = nullptr;
+    auto cleanup = [&]() { dfree(d_o); dfree(d_d); dfree(d_t); dfree(d_s); dfree(d_f); };
+    hipError_t e;
+    if ((e = hipMalloc((void**)&d_o, n * 12)) != hipSuccess || (e = hipMalloc((void**)&d_d, n * 12)) != hipSuccess ||
+        (e = hipMalloc((void**)&d_t, n * 4)) != hipSuccess || (e = hipMalloc((void**)&d_s, n * 4)) != hipSuccess ||
+        (e = hipMalloc((void**)&d_f, n * 4)) != hipSuccess ||
+        (e = hipMemcpyAsync(d_o, org, n * 12, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(d_d, dir, n * 12, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
+        (e = rt_launch_np_trace(c->d_np, c->hdr.n_np, (uint32_t)n, d_o, d_d, d_s, d_t, d_f, c->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(sphere, d_s, n * 4, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(t, d_t, n * 4, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(front, d_f, n * 4, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(c->stream)) != hipSuccess) {
+        cleanup(); return hip_fail(c, e, "rt_np_trace");
+    }
+    cleanup();
+    return RT_OK;
+}
+
 void rt_denoise_params_default(rt_denoise_params* p)
 {
     if (!p) return;
@@ -1297,6 +1434,7 @@ rt_status rt_trace(rt_ctx* c, uint64_t n, const float* org, const float* dir, in
 {
     if (!c || (n && (!org || !dir || !tri || !t))) return RT_ERR_INVALID;
     if (!c->has_scene) { c->err = "no scene uploaded"; return RT_ERR_STATE; }
+    if (c->hdr.n_np > 0) { c->err = "a non-physical path tracer scene traces with rt_np_trace"; return RT_ERR_STATE; }
     if (n == 0) return RT_OK;
     if (n > 0x7FFFFFFFull) return RT_ERR_INVALID;
     HIPC(c, hipSetDevice(c->device));

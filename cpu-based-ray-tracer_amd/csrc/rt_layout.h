@@ -61,6 +61,7 @@ typedef struct {
     uint32_t n_lboxes;         // distinct leaf boxes of a small scene (<= 64 triangles), 0 otherwise
     uint32_t has_vboxes;       // every leaf box is its triangle's vertex box (FlatScene::tabc holds the vertices)
     uint32_t n_spheres;        // sphere entities (their slots in `tris` carry the sphere flag)
+    uint32_t n_np;             // spheres of a non-physical path tracer scene (rt_np.h; every other count is 0)
 } rt_scene_header;
 
 // tabc (when hdr.has_vboxes; the Whitted half-plane walk's exact leaf boxes): 3 x float4 per triangle slot:

@@ -412,6 +412,19 @@ void SceneBuilder::add_two_spheres_scene()
     add_point_light(PointLight{{30.0f, 50.0f, -12.0f}, {0.5f, 0.5f, 0.5f}});
 }
 
+void SceneBuilder::add_np_scene()
+{
+    // NP/mainloop.cpp:30-40: the materials' double literals narrowed to float as ColorRGB / the constructors take them
+    const F3 ground{(float)0.8, (float)0.8, (float)0.0}, back{(float)0.1, (float)0.2, (float)0.5};
+    const F3 left{(float)0.8, (float)0.2, (float)0.2}, right{(float)0.8, (float)0.6, (float)0.2}, none{0.0f, 0.0f, 0.0f};
+    add_np_sphere(NpSphere{{0.0f, (float)-100.5, -1.0f}, 100.0f, 0, ground, 0.0f, 1.0f});
+    add_np_sphere(NpSphere{{0.0f, 0.0f, -3.0f}, (float)0.5, 0, back, 0.0f, 1.0f});
+    add_np_sphere(NpSphere{{-1.0f, 0.0f, -1.0f}, (float)0.5, 1, left, 0.0f, 1.0f});
+    add_np_sphere(NpSphere{{0.0f, 2.0f, -2.0f}, (float)0.5, 2, none, 0.0f, (float)1.5});
+    add_np_sphere(NpSphere{{0.0f, 2.0f, -2.0f}, (float)-0.05, 2, none, 0.0f, (float)1.5});
+    add_np_sphere(NpSphere{{1.0f, 0.0f, -1.0f}, (float)0.5, 1, right, (float)0.5, 1.0f});
+}
+
 // World entities -> went / wtris (rt_layout.h)
 static void flatten_world(const std::vector<WorldEntity>& world, FlatScene& out)
 {
@@ -449,6 +462,21 @@ bool SceneBuilder::build(FlatScene& out, std::string& err) const
     int sah_bins = 16;
     if (const char* e = rt_knob("RT_SAH_BINS")) sah_bins = std::min(std::max((int)std::strtol(e, nullptr, 10), 2), kMaxSahBins);
     const size_t nm = meshes_.size();
+    if (!np_.empty()) {
+        // a non-physical path tracer scene: the spheres in insertion order, no tree (NP/Hittable.h:64-81)
+        if (has_other_than_np()) { err = "a scene holds either non-physical path tracer spheres or anything else, not both"; return false; }
+        if (np_.size() > 65536) { err = "more than 65536 non-physical path tracer spheres"; return false; }
+        for (const auto& s : np_) {
+            // Metal::Metal clamps the fuzziness (NP/Material.h:75); radius * radius is Sphere::is_hit_by's own product
+            const float fuzz = s.fuzziness < 1.0f ? s.fuzziness : 1.0f;
+            const float q[12] = {s.center.x, s.center.y, s.center.z, s.radius, s.radius * s.radius, bits_as_float(s.kind), fuzz,
+                                 s.refractive_index, s.albedo.x, s.albedo.y, s.albedo.z, 0.0f};
+            out.npsph.insert(out.npsph.end(), q, q + 12);
+        }
+        out.hdr.n_np = (uint32_t)np_.size();
+        out.hdr.light_mesh = -1;
+        return true;
+    }
     for (const auto& e : world_) {
         if (e.kind == 0 && !(e.radius > 0.0f)) { err = "world sphere with a non-positive radius"; return false; }
         if (e.kind == 1) {

@@ -46,11 +46,22 @@ struct WorldEntity {
     F3 diffuse_color{0.2f, 0.2f, 0.2f};
 };
 
+// A sphere of the non-physical path tracer (NP/Hittable.h:98-141 with its NP/Material.h material).
+// kind: 0 Diffuse, 1 Metal, 2 Dielectric; the radius may be negative (NP/Material.h:113-119).
+struct NpSphere {
+    F3 center{0, 0, 0};
+    float radius = 0.0f;
+    int kind = 0;
+    F3 albedo{0, 0, 0};
+    float fuzziness = 0.0f, refractive_index = 1.0f;
+};
+
 // Flattened, upload-ready scene (rt_layout.h).
 struct FlatScene {
     rt_scene_header hdr{};
     std::vector<float> nodes, tris, mats, lnodes, ltris, wmats, plights;   // float4-granular
     std::vector<float> went, wtris;                                       // Whitted world (C1)
+    std::vector<float> npsph;                                             // non-physical path tracer spheres (rt_np.h)
     std::vector<float> lboxes;                                            // distinct leaf boxes (small scenes)
     // split trace (larger scenes, the vertex kernel's BVH variant): the subtree [split_root, split_end) of
     // the DFS pre-order is walked; the <= 32 leaves outside it are tested by their distinct leaf boxes
@@ -99,6 +110,12 @@ public:
     int add_world_entity(WorldEntity e) { world_.push_back(std::move(e)); return (int)world_.size() - 1; }
     // the world of the Whitted Style Ray Tracer's Renderer::Renderer() (WH/Renderer.cpp:27-49)
     void add_two_spheres_scene();
+    // CompositeHittable::add(Sphere) of the non-physical path tracer (NP/Hittable.h:59-62); such a scene holds nothing else
+    int add_np_sphere(const NpSphere& s) { np_.push_back(s); return (int)np_.size() - 1; }
+    // the world of its CSC8599Layer() (NP/mainloop.cpp:30-40)
+    void add_np_scene();
+    size_t num_np() const { return np_.size(); }
+    bool has_other_than_np() const { return !meshes_.empty() || !world_.empty() || !lights_.empty(); }
     // Renderer::GenerateBVH (MC/Renderer.h:83-86) + TriangleMesh's per-mesh BVH (MC/TriangleMesh.h:185)
     bool build(FlatScene& out, std::string& err) const;
     size_t num_meshes() const { return meshes_.size(); }
@@ -108,6 +125,7 @@ private:
     std::vector<MeshDesc> meshes_;
     std::vector<PointLight> lights_;
     std::vector<WorldEntity> world_;
+    std::vector<NpSphere> np_;
     F3 sky_{0.2f, 0.7f, 0.8f};   // BV/Renderer.h:189
 };
 

@@ -25,6 +25,10 @@
  *   rt_scene_add_two_spheres_scene        Whitted Style Ray Tracer Renderer::Renderer()       WH/Renderer.cpp:27-49
  *   rt_render + RT_RENDER_WHITTED on a    Whitted Style Ray Tracer RayGen_Shader /           WH/Renderer.cpp:82-125,
  *     world scene                         cast_Whitted_ray                                   WH/Renderer.h:184-310
+ *   rt_scene_add_np_sphere / _np_scene    non physical path tracer Sphere + CompositeHittable::add, CSC8599Layer()
+ *                                         (NP/Hittable.h:59-62,98-102, NP/mainloop.cpp:30-40)
+ *   rt_render_np                          non physical path tracer Renderer::Render / ray_color   NP/Renderer.cpp:56-132
+ *   rt_np_trace                           CompositeHittable::is_hit_by                          NP/Hittable.h:64-81
  */
 #ifndef RT_CAPI_H
 #define RT_CAPI_H
@@ -108,6 +112,25 @@ rt_status rt_scene_add_two_spheres_scene(rt_scene* s);
  * with spheres render on the megakernel (rt_stats.kernel_reason RT_KERNEL_REASON_SPHERES). */
 rt_status rt_scene_add_sphere(rt_scene* s, const float center[3], float radius, const float albedo[3], const float emission[3],
                               int32_t* entity_id);
+/* The "non physical path tracer" (NP/ = non physical path tracer/8599RayTracerGUI/src/): spheres with Diffuse /
+ * Metal / Dielectric materials (NP/Material.h:24-146) in a CompositeHittable, intersected brute force in insertion
+ * order (NP/Hittable.h:64-134).  A scene holds either such spheres or anything else (mixing: RT_ERR_INVALID);
+ * rt_scene_build builds no tree and rt_scene_info reads all zero for it.  Rendered by rt_render_np. */
+#define RT_NP_DIFFUSE 0
+#define RT_NP_METAL 1
+#define RT_NP_DIELECTRIC 2
+typedef struct {
+    int32_t kind;             /* RT_NP_DIFFUSE / RT_NP_METAL / RT_NP_DIELECTRIC */
+    float albedo[3];          /* Diffuse, Metal */
+    float fuzziness;          /* Metal; clamped as f < 1 ? f : 1 (NP/Material.h:75) */
+    float refractive_index;   /* Dielectric; > 0 */
+} rt_np_material;
+/* Sphere(center, radius, material) + CompositeHittable::add: the radius may be negative (a hollow, NP/Material.h:113-119)
+ * but not zero; every float finite and the index > 0, else RT_ERR_INVALID.  id = the sphere's index. */
+rt_status rt_scene_add_np_sphere(rt_scene* s, const float center[3], float radius, const rt_np_material* m, int32_t* id);
+/* the six spheres of CSC8599Layer() (NP/mainloop.cpp:30-40), in that order */
+rt_status rt_scene_add_np_scene(rt_scene* s);
+rt_status rt_scene_np_count(const rt_scene* s, uint32_t* n);
 rt_status rt_scene_build(rt_scene* s);
 
 typedef struct {
@@ -221,6 +244,26 @@ typedef struct {
  * asynchronous renders until such a call reads it, so an earlier render's loss is reported even when a
  * later render lost nothing. */
 rt_status rt_render(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p, uint32_t* out_rgba, float* out_accum);
+/* Renderer::Render x n_frames of the non-physical path tracer (NP/Renderer.cpp:56-132) on a scene of
+ * rt_scene_add_np_sphere spheres: ray_color to bounce depth 50 with the sky gradient, accumulation += (rgb, 1) per
+ * frame, and the last frame's accumulation / frame, pow(., 1.0f / gamma), clamp, ABGR pack.  The contract of
+ * rt_render: asynchronous unless an output pointer is given, the accumulation reset when first_frame == 1, the row
+ * bands of rt_resize, rt_stats.last_kernel_ms / last_main_ms, rt_stats.kernel == RT_KERNEL_NP.  Samples are keyed by
+ * (global pixel, frame): draws 0, 1 jitter the camera ray as in rt_render.  RT_ERR_STATE on any other scene (and
+ * rt_render on such a scene). */
+typedef struct {
+    uint32_t first_frame; /* 1-based frame index of the first sample */
+    uint32_t n_frames;
+    uint64_t seed;
+    int32_t diffuse_model; /* 0 IN_Sphere, 1 ON_Sphere (default), 2 IN_Hemisphere (NP/NPPTToolbox.h:25-38) */
+    int32_t gamma;         /* >= 1, default 1 (NP/NPPTToolbox.h:40-44) */
+    uint32_t flags;        /* RT_RENDER_EXACT (the attenuation product folded inner-first, as the recursion returns it) or 0 */
+} rt_np_params;
+void rt_np_params_default(rt_np_params* p);
+rt_status rt_render_np(rt_ctx* ctx, const rt_camera* cam, const rt_np_params* p, uint32_t* out_rgba, float* out_accum);
+/* CompositeHittable::is_hit_by(ray, 0.001, infinity) (NP/Hittable.h:64-81) of n rays (host arrays) on the device, by the
+ * render kernel's intersection routine: sphere index or -1, t (+inf on a miss), is_hitting_front_face (0 / 1) */
+rt_status rt_np_trace(rt_ctx* ctx, uint64_t n, const float* org, const float* dir, int32_t* sphere, float* t, int32_t* front);
 /* device pointers of the local accumulation (float4) and RGBA8 buffers */
 rt_status rt_device_buffers(rt_ctx* ctx, void** d_accum, void** d_rgba);
 /* copy the local float4 accumulation (local_rows x W x 4 floats) to host memory after synchronising with
@@ -263,7 +306,8 @@ typedef struct {
 #define RT_KERNEL_VERTEX 1    /* pt_coherent_kernel (rt_coherent.hip): small scenes, vertex-synchronous */
 #define RT_KERNEL_WHITTED 2   /* whitted_kernel / whitted_world_kernel (rt_whitted.hip) */
 #define RT_KERNEL_VERTEX_BVH 3   /* pt_coherent_kernel's BVH variant (rt_coherent.hip): other path scenes */
-#define RT_KERNEL_REASON_DEFAULT 0       /* the kernel the scene calls for */
+#define RT_KERNEL_NP 4        /* np_kernel (rt_np.hip): rt_render_np */
+#define RT_KERNEL_REASON_DEFAULT 0      /* the kernel the scene calls for */
 #define RT_KERNEL_REASON_TABLES_LDS 1    /* megakernel: the BVH variant stages the material and light tables (and a
                                             split scene's outside triangles) in LDS, and they exceed its 40 KB
                                             (about 2500 light triangles or 1280 materials); a large slowdown */
