@@ -175,6 +175,7 @@ def lib():
         "rt_camera_look_ex": (i32, [u32, u32, fp, fp, C.c_float, C.c_float, C.c_float, C.POINTER(Camera), fp, fp]),
         "rt_denoise_params_default": (None, [C.POINTER(DenoiseParams)]),
         "rt_render_denoised": (i32, [vp, C.POINTER(Camera), fp, fp, u32, u64, C.c_float, C.POINTER(DenoiseParams), C.POINTER(u32), fp]),
+        "rt_render_denoised_atrous": (i32, [vp, C.POINTER(Camera), fp, fp, u32, u64, C.c_float, C.POINTER(DenoiseParams), i32, C.POINTER(u32), fp]),
         "rt_denoise_restart": (i32, [vp]),
         "rt_get_gbuffer": (i32, [vp, fp, fp, fp, C.POINTER(i32), fp]),
         "rt_scene_add_np_sphere": (i32, [vp, fp, C.c_float, C.POINTER(NpMaterial), C.POINTER(i32)]),
@@ -706,6 +707,16 @@ class Context:
         self._check(lib().rt_render_denoised(self.h, C.byref(cam), _fp(proj), _fp(view), frame, seed, rr, C.byref(params), None, None),
                     "rt_render_denoised")
         return None
+
+    def render_denoised_atrous(self, cam, proj, view, frame, params, levels, seed=0, rr=0.8, fetch=True):
+        """render_denoised with the a-trous wavelet filter of `levels` (1 .. 8) levels as the spatial pass (csrc/rt_atrous.hip)."""
+        proj = np.ascontiguousarray(proj, np.float32); view = np.ascontiguousarray(view, np.float32)
+        rgba = np.zeros((self.H, self.W), np.uint32) if fetch else None
+        col = np.zeros((self.H, self.W, 4), np.float32) if fetch else None
+        self._check(lib().rt_render_denoised_atrous(self.h, C.byref(cam), _fp(proj), _fp(view), frame, seed, rr, C.byref(params), levels,
+                                                    rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if fetch else None,
+                                                    _fp(col) if fetch else None), "rt_render_denoised_atrous")
+        return (rgba, col) if fetch else None
 
     def denoise_restart(self):
         self._check(lib().rt_denoise_restart(self.h), "rt_denoise_restart")

@@ -90,6 +90,7 @@ struct rt_ctx {
     float4 *d_gb_color = nullptr, *d_gb_pos = nullptr, *d_gb_nrm = nullptr, *d_spatial = nullptr, *d_temporal = nullptr, *d_prev_color = nullptr;
     int32_t *d_gb_prim = nullptr, *d_prev_prim = nullptr;
     uint32_t *d_dn_rgba = nullptr;
+    float4 *d_dn_scratch = nullptr;   // the a-trous filter's second level buffer
     size_t dn_pixels = 0;
     bool have_prev = false;
     float prev_proj[16] = {}, prev_view[16] = {};
@@ -604,7 +605,7 @@ void rt_destroy(rt_ctx* c)
     dfree(c->d_tabc);
     dfree(c->d_went); dfree(c->d_wtris); dfree(c->d_np);
     dfree(c->d_gb_color); dfree(c->d_gb_pos); dfree(c->d_gb_nrm); dfree(c->d_spatial); dfree(c->d_temporal); dfree(c->d_prev_color);
-    dfree(c->d_gb_prim); dfree(c->d_prev_prim); dfree(c->d_dn_rgba); dfree(c->d_lbuf); dfree(c->d_sky);
+    dfree(c->d_gb_prim); dfree(c->d_prev_prim); dfree(c->d_dn_rgba); dfree(c->d_dn_scratch); dfree(c->d_lbuf); dfree(c->d_sky);
     dfree(c->d_crec); dfree(c->d_seg_list); dfree(c->d_tile_boxes);
     if (c->ev2) (void)hipEventDestroy(c->ev2);
     if (c->ev3) (void)hipEventDestroy(c->ev3);
@@ -1259,8 +1260,10 @@ rt_status rt_denoise_restart(rt_ctx* c)
     return RT_OK;
 }
 
-rt_status rt_render_denoised(rt_ctx* c, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame, uint64_t seed, float rr,
-                             const rt_denoise_params* dp, uint32_t* out_rgba, float* out_color)
+// one denoised frame; atrous_levels > 0: the a-trous wavelet filter is the spatial pass (rt_atrous.hip), else the
+// joint bilateral filter
+static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame, uint64_t seed, float rr,
+                                 const rt_denoise_params* dp, int atrous_levels, uint32_t* out_rgba, float* out_color)
 {
     if (!c || !cam || !proj || !view || !dp) return RT_ERR_INVALID;
     if (!c->has_scene || c->hdr.n_nodes == 0) { c->err = "no triangle scene uploaded"; return RT_ERR_STATE; }
@@ -1275,8 +1278,8 @@ rt_status rt_render_denoised(rt_ctx* c, const rt_camera* cam, const float proj[1
     if (c->dn_pixels != npx) {
         HIPC(c, hipStreamSynchronize(c->stream));
         dfree(c->d_gb_color); dfree(c->d_gb_pos); dfree(c->d_gb_nrm); dfree(c->d_spatial); dfree(c->d_temporal); dfree(c->d_prev_color);
-        dfree(c->d_gb_prim); dfree(c->d_prev_prim); dfree(c->d_dn_rgba);
-        float4** f4[6] = {&c->d_gb_color, &c->d_gb_pos, &c->d_gb_nrm, &c->d_spatial, &c->d_temporal, &c->d_prev_color};
+        dfree(c->d_gb_prim); dfree(c->d_prev_prim); dfree(c->d_dn_rgba); dfree(c->d_dn_scratch);
+        float4** f4[7] = {&c->d_gb_color, &c->d_gb_pos, &c->d_gb_nrm, &c->d_spatial, &c->d_temporal, &c->d_prev_color, &c->d_dn_scratch};
         for (float4** q : f4) HIPC(c, hipMalloc((void**)q, npx * sizeof(float4)));
         HIPC(c, hipMalloc((void**)&c->d_gb_prim, npx * 4));
         HIPC(c, hipMalloc((void**)&c->d_prev_prim, npx * 4));
@@ -1293,12 +1296,13 @@ rt_status rt_render_denoised(rt_ctx* c, const rt_camera* cam, const float proj[1
     rt_status st = rt_render(c, cam, &rp, nullptr, nullptr);
     c->gb_next = false;
     if (st != RT_OK) return st;
-    // 2) joint bilateral + 3) temporal (+ pack)
+    // 2) joint bilateral or a-trous levels + 3) temporal (+ pack)
     const bool temporal = dp->temporal_half_size > 0;
     DenoiseParams D{};
     D.W = (int)c->W; D.H = (int)c->H;
     D.color = c->d_gb_color; D.pos = c->d_gb_pos; D.nrm = c->d_gb_nrm; D.prim = c->d_gb_prim;
-    D.spatial = dp->jbf_half_size > 0 ? c->d_spatial : c->d_gb_color;
+    D.spatial = (dp->jbf_half_size > 0 || atrous_levels > 0) ? c->d_spatial : c->d_gb_color;
+    D.atrous_levels = atrous_levels; D.scratch = c->d_dn_scratch;
     D.prev_color = c->d_prev_color; D.prev_prim = c->d_prev_prim;
     D.temporal = c->d_temporal; D.rgba = c->d_dn_rgba;
     D.jbf_half = dp->jbf_half_size; D.immediate_clamp = dp->immediate_clamp != 0;
@@ -1324,6 +1328,20 @@ rt_status rt_render_denoised(rt_ctx* c, const rt_camera* cam, const float proj[1
     if (out_color) HIPC(c, hipMemcpyAsync(out_color, c->d_temporal, npx * 16, hipMemcpyDeviceToHost, c->stream));
     if (out_rgba || out_color) HIPC(c, hipStreamSynchronize(c->stream));
     return RT_OK;
+}
+
+rt_status rt_render_denoised(rt_ctx* c, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame, uint64_t seed, float rr,
+                             const rt_denoise_params* dp, uint32_t* out_rgba, float* out_color)
+{
+    return render_denoised(c, cam, proj, view, frame, seed, rr, dp, 0, out_rgba, out_color);
+}
+
+rt_status rt_render_denoised_atrous(rt_ctx* c, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame, uint64_t seed,
+                                    float rr, const rt_denoise_params* dp, int32_t levels, uint32_t* out_rgba, float* out_color)
+{
+    if (!c) return RT_ERR_INVALID;
+    if (levels < 1 || levels > 8) { c->err = "a-trous levels must be in 1 .. 8"; return RT_ERR_INVALID; }
+    return render_denoised(c, cam, proj, view, frame, seed, rr, dp, levels, out_rgba, out_color);
 }
 
 rt_status rt_get_gbuffer(rt_ctx* c, float* color, float* position, float* normal, int32_t* prim, float* spatial)

@@ -300,7 +300,10 @@ hipError_t rt_launch_denoise(const DenoiseParams& D, hipStream_t stream)
 {
     const uint32_t tiles = (uint32_t)(((D.W + 15) / 16) * ((D.H + 15) / 16));
     if (tiles == 0) return hipSuccess;
-    if (D.jbf_half > 0) {
+    if (D.atrous_levels > 0) {
+        const hipError_t e = rt_launch_atrous(D, stream);
+        if (e != hipSuccess) return e;
+    } else if (D.jbf_half > 0) {
         DenoiseParams Dl = D;
         Dl.ieee_div = rt_knob("RT_JBF_IEEE") ? 1 : 0;   // diagnostic: every division by the IEEE sequence (tests)
         if (D.jbf_half <= JB_MAX_HALF && !rt_knob("RT_JBF_GLOBAL")) {

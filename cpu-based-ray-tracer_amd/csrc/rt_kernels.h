@@ -166,8 +166,14 @@ struct DenoiseParams {
     int temporal_half; float tolerance, weighting; int have_prev;
     float prev_proj[16], prev_view[16];
     int ieee_div;   // diagnostic (RT_JBF_IEEE): the filter's divisions by the IEEE sequence, not Markstein's correction
+    // > 0: the spatial pass is the a-trous wavelet filter of that many levels (rt_atrous.hip) instead of the joint
+    // bilateral filter (jbf_half is ignored); its levels ping-pong between `scratch` and `spatial`
+    int atrous_levels;
+    float4* scratch;
 };
 hipError_t rt_launch_denoise(const DenoiseParams& D, hipStream_t stream);
+// the a-trous levels alone (D.atrous_levels in 1 .. 8): D.color -> D.spatial (called by rt_launch_denoise)
+hipError_t rt_launch_atrous(const DenoiseParams& D, hipStream_t stream);
 
 // GPU BVH build (rt_lbvh.hip): a Karras LBVH in the traversal layout (rt_layout.h nodes / tris).
 // verts: 9 floats per triangle (a, b, c); recs: the triangle records (4 float4 per triangle); n >= 2.

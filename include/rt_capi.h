@@ -20,6 +20,7 @@
  *   rt_scene_add_bvh_tracer_scene         BVH Ray Tracer Renderer::Renderer()                  BV/Renderer.cpp:26-43
  *   rt_render_denoised                    Denoiser project Renderer::Render (G-buffer, JBF,    DN/Renderer.cpp:101-311,
  *                                         temporal filter)                                   DN/Denoiser.h:133-328
+ *   rt_render_denoised_atrous             (no reference counterpart: the same frame with an a-trous wavelet spatial pass)
  *   rt_scene_add_world_sphere / _mesh     Whitted Style Ray Tracer Sphere / TriangleMesh + World::Add
  *                                         (WH/Sphere.h:16-75, WH/TriangleMesh.h:47-155, WH/World.h:37-45)
  *   rt_scene_add_two_spheres_scene        Whitted Style Ray Tracer Renderer::Renderer()       WH/Renderer.cpp:27-49
@@ -288,7 +289,7 @@ typedef struct {
     /* RT_RENDER_COUNT: wave-level fold iterations; wave cycles (s_memtime) spent in service,
      * work-queue + camera-ray, and traversal rounds; lanes served per service round (sum) */
     uint64_t wave_fold, cycles_service, cycles_queue, cycles_trace, service_lanes;
-    float last_denoise_ms;    /* rt_render_denoised: the joint bilateral + temporal kernels (HIP events) */
+    float last_denoise_ms;    /* rt_render_denoised[_atrous]: the spatial + temporal kernels (HIP events) */
     uint32_t n_chunks;        /* frame chunks per pixel of the last rt_render's (last) launch: 1 unless the
                                  launch has few pixels per lane; last_kernel_ms covers the in-order finalize */
     uint32_t n_passes;        /* launches over consecutive frame ranges (bounded parked-sample memory) */
@@ -379,6 +380,14 @@ void rt_denoise_params_default(rt_denoise_params* p);
  * out_rgba (W x H u32) / out_color (W x H x 4 f32: the temporal output) may be NULL */
 rt_status rt_render_denoised(rt_ctx* ctx, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame, uint64_t seed,
                              float rr, const rt_denoise_params* p, uint32_t* out_rgba, float* out_color);
+/* the same frame with the edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) as the spatial pass instead of
+ * the joint bilateral filter: `levels` (1 .. 8) passes of a 5 x 5 B3-spline kernel whose taps sit 2^l pixels apart,
+ * with the joint bilateral filter's edge-stopping weights and sigmas (a footprint of +-2 (2^levels - 1) pixels at 25
+ * taps per level; p->jbf_half_size is ignored).  Not the reference's filter and not bit-exact to any CPU original
+ * (DESIGN.md 5.7).  The temporal filter, the pack, the history and rt_get_gbuffer are shared with rt_render_denoised:
+ * frames filtered either way may follow each other. */
+rt_status rt_render_denoised_atrous(rt_ctx* ctx, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame,
+                                    uint64_t seed, float rr, const rt_denoise_params* p, int32_t levels, uint32_t* out_rgba, float* out_color);
 rt_status rt_denoise_restart(rt_ctx* ctx);
 /* the last denoised frame's buffers (W x H each; any pointer may be NULL): G-buffer color / world
  * position / normal (4 floats per pixel), primitive id (-1: primary ray missed), joint bilateral output */

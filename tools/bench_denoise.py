@@ -1,0 +1,54 @@
+#!/usr/bin/env python3
+"""tools/bench_denoise.py -- the denoiser's spatial + temporal kernels on one GPU, Cornell box at 1920x1080: the joint
+bilateral filter (half sizes 16 and 32) and the a-trous wavelet filter (3, 4, 5 levels), one JSON line each.
+
+One process; each repeat is one denoised frame with the temporal filter on (half size 3) and the default sigmas, timed by
+the library's HIP events around the filters (rt_stats.last_denoise_ms); warm-up frames of the same case come first.
+"""
+import argparse
+import hashlib
+import importlib.util
+import json
+import os
+import statistics
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(REPO, "cpu-based-ray-tracer_amd")
+CASES = [("jbf", 16), ("jbf", 32), ("atrous", 3), ("atrous", 4), ("atrous", 5)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=15)
+    a = ap.parse_args()
+    spec = importlib.util.spec_from_file_location("rt_amd", os.path.join(PKG, "__init__.py"))
+    rt = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rt)
+    ctx = rt.Context(0)   # raises without a GPU: there is no other path
+    ctx.upload(rt.Scene.cornell())
+    ctx.resize(a.width, a.height)
+    cam, proj, view = rt.camera_look_ex(a.width, a.height, rt.DEFAULT_CAMERA_POSITION, rt.DEFAULT_CAMERA_FORWARD)
+    sha = hashlib.sha256(open(rt.LIB_PATH, "rb").read()).hexdigest()[:16]
+    for kind, n in CASES:
+        params = rt.denoise_params(jbf_half_size=n if kind == "jbf" else 0, temporal_half_size=3)
+        ms = []
+        for i in range(a.warmup + a.repeats):
+            if kind == "jbf":
+                ctx.render_denoised(cam, proj, view, i + 1, params, seed=1, fetch=False)
+            else:
+                ctx.render_denoised_atrous(cam, proj, view, i + 1, params, n, seed=1, fetch=False)
+            st = ctx.stats()   # synchronises with the frame's events
+            if i >= a.warmup:
+                ms.append(st.last_denoise_ms)
+        med = statistics.median(ms)
+        print(json.dumps({"bench": "denoise", "filter": kind, "half_size" if kind == "jbf" else "levels": n, "width": a.width,
+                          "height": a.height, "warmup": a.warmup, "repeats": a.repeats, "ms": [round(m, 3) for m in ms],
+                          "median_ms": round(med, 3), "spread_pct": round(100.0 * (max(ms) - min(ms)) / med, 2), "lib_sha256": sha}), flush=True)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
