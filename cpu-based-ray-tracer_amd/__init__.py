@@ -176,6 +176,8 @@ def lib():
         "rt_denoise_params_default": (None, [C.POINTER(DenoiseParams)]),
         "rt_render_denoised": (i32, [vp, C.POINTER(Camera), fp, fp, u32, u64, C.c_float, C.POINTER(DenoiseParams), C.POINTER(u32), fp]),
         "rt_render_denoised_atrous": (i32, [vp, C.POINTER(Camera), fp, fp, u32, u64, C.c_float, C.POINTER(DenoiseParams), i32, C.POINTER(u32), fp]),
+        "rt_render_denoised_svgf": (i32, [vp, C.POINTER(Camera), fp, fp, u32, u64, C.c_float, C.POINTER(DenoiseParams), i32, C.c_float, C.POINTER(u32), fp]),
+        "rt_get_variance": (i32, [vp, fp, fp]),
         "rt_denoise_restart": (i32, [vp]),
         "rt_get_gbuffer": (i32, [vp, fp, fp, fp, C.POINTER(i32), fp]),
         "rt_scene_add_np_sphere": (i32, [vp, fp, C.c_float, C.POINTER(NpMaterial), C.POINTER(i32)]),
@@ -717,6 +719,23 @@ class Context:
                                                     rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if fetch else None,
                                                     _fp(col) if fetch else None), "rt_render_denoised_atrous")
         return (rgba, col) if fetch else None
+
+    def render_denoised_svgf(self, cam, proj, view, frame, params, levels, sigma_luminance=4.0, seed=0, rr=0.8, fetch=True):
+        """render_denoised with SVGF's spatial stage as the spatial pass (csrc/rt_svgf.hip): a windowed luminance variance, then
+        `levels` (1 .. 8) a-trous levels whose color edge-stop it scales (params.sigma_color is ignored)."""
+        proj = np.ascontiguousarray(proj, np.float32); view = np.ascontiguousarray(view, np.float32)
+        rgba = np.zeros((self.H, self.W), np.uint32) if fetch else None
+        col = np.zeros((self.H, self.W, 4), np.float32) if fetch else None
+        self._check(lib().rt_render_denoised_svgf(self.h, C.byref(cam), _fp(proj), _fp(view), frame, seed, rr, C.byref(params), levels,
+                                                  sigma_luminance, rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if fetch else None,
+                                                  _fp(col) if fetch else None), "rt_render_denoised_svgf")
+        return (rgba, col) if fetch else None
+
+    def variance(self):
+        """The last render_denoised_svgf frame's luminance variance: the initial estimate and the last level's."""
+        v0 = np.zeros((self.H, self.W), np.float32); vl = np.zeros((self.H, self.W), np.float32)
+        self._check(lib().rt_get_variance(self.h, _fp(v0), _fp(vl)), "rt_get_variance")
+        return dict(initial=v0, filtered=vl)
 
     def denoise_restart(self):
         self._check(lib().rt_denoise_restart(self.h), "rt_denoise_restart")

@@ -25,12 +25,10 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "rt_atrous_tile.h"   // AT_PITCH .. AT_BH, acos_unit: shared with rt_svgf.hip
 #include "rt_kernels.h"
 
 namespace {
-
-constexpr int AT_PITCH = 96, AT_HALF = 48, AT_PAIRS = 5;   // 9 planes in 5 row-sets of two
-constexpr int AT_BW = 32, AT_BH = 8;                       // cells filtered by a workgroup
 
 struct AtrousLevel {
     int W, H;
@@ -40,20 +38,6 @@ struct AtrousLevel {
     int step, clamp;
     float ep, ec, en, ek;            // -log2(e) / (2 sigma^2): the weight is exp2 of the weighted sum
 };
-
-// acos on [0, 1]: sqrt(1 - x) * p7(x), Abramowitz & Stegun 4.4.46 (|error| <= 2e-8); 1 - x is exact for x >= 1/2
-__device__ __forceinline__ float acos_unit(float x)
-{
-    float p = -0.0012624911f;
-    p = p * x + 0.0066700901f;
-    p = p * x - 0.0170881256f;
-    p = p * x + 0.0308918810f;
-    p = p * x - 0.0501743046f;
-    p = p * x + 0.0889789874f;
-    p = p * x - 0.2145988016f;
-    p = p * x + 1.5707963050f;
-    return __builtin_amdgcn_sqrtf(1.0f - x) * p;
-}
 
 template <int DC, int DR>
 __global__ void __launch_bounds__(256) atrous_kernel(AtrousLevel A)

@@ -91,6 +91,8 @@ struct rt_ctx {
     int32_t *d_gb_prim = nullptr, *d_prev_prim = nullptr;
     uint32_t *d_dn_rgba = nullptr;
     float4 *d_dn_scratch = nullptr;   // the a-trous filter's second level buffer
+    float *d_dn_var = nullptr;        // rt_render_denoised_svgf: three W x H planes (Var_0, Var_L, the levels' other buffer)
+    bool svgf_last = false;           // the last denoised frame was an SVGF one (rt_get_variance)
     size_t dn_pixels = 0;
     bool have_prev = false;
     float prev_proj[16] = {}, prev_view[16] = {};
@@ -605,7 +607,7 @@ void rt_destroy(rt_ctx* c)
     dfree(c->d_tabc);
     dfree(c->d_went); dfree(c->d_wtris); dfree(c->d_np);
     dfree(c->d_gb_color); dfree(c->d_gb_pos); dfree(c->d_gb_nrm); dfree(c->d_spatial); dfree(c->d_temporal); dfree(c->d_prev_color);
-    dfree(c->d_gb_prim); dfree(c->d_prev_prim); dfree(c->d_dn_rgba); dfree(c->d_dn_scratch); dfree(c->d_lbuf); dfree(c->d_sky);
+    dfree(c->d_gb_prim); dfree(c->d_prev_prim); dfree(c->d_dn_rgba); dfree(c->d_dn_scratch); dfree(c->d_dn_var); dfree(c->d_lbuf); dfree(c->d_sky);
     dfree(c->d_crec); dfree(c->d_seg_list); dfree(c->d_tile_boxes);
     if (c->ev2) (void)hipEventDestroy(c->ev2);
     if (c->ev3) (void)hipEventDestroy(c->ev3);
@@ -1260,10 +1262,10 @@ rt_status rt_denoise_restart(rt_ctx* c)
     return RT_OK;
 }
 
-// one denoised frame; atrous_levels > 0: the a-trous wavelet filter is the spatial pass (rt_atrous.hip), else the
-// joint bilateral filter
+// one denoised frame; atrous_levels > 0: the a-trous wavelet filter is the spatial pass (rt_atrous.hip), variance-guided
+// (rt_svgf.hip) when sigma_luminance > 0; else the joint bilateral filter
 static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame, uint64_t seed, float rr,
-                                 const rt_denoise_params* dp, int atrous_levels, uint32_t* out_rgba, float* out_color)
+                                 const rt_denoise_params* dp, int atrous_levels, float sigma_luminance, uint32_t* out_rgba, float* out_color)
 {
     if (!c || !cam || !proj || !view || !dp) return RT_ERR_INVALID;
     if (!c->has_scene || c->hdr.n_nodes == 0) { c->err = "no triangle scene uploaded"; return RT_ERR_STATE; }
@@ -1278,16 +1280,18 @@ static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float pr
     if (c->dn_pixels != npx) {
         HIPC(c, hipStreamSynchronize(c->stream));
         dfree(c->d_gb_color); dfree(c->d_gb_pos); dfree(c->d_gb_nrm); dfree(c->d_spatial); dfree(c->d_temporal); dfree(c->d_prev_color);
-        dfree(c->d_gb_prim); dfree(c->d_prev_prim); dfree(c->d_dn_rgba); dfree(c->d_dn_scratch);
+        dfree(c->d_gb_prim); dfree(c->d_prev_prim); dfree(c->d_dn_rgba); dfree(c->d_dn_scratch); dfree(c->d_dn_var);
         float4** f4[7] = {&c->d_gb_color, &c->d_gb_pos, &c->d_gb_nrm, &c->d_spatial, &c->d_temporal, &c->d_prev_color, &c->d_dn_scratch};
         for (float4** q : f4) HIPC(c, hipMalloc((void**)q, npx * sizeof(float4)));
         HIPC(c, hipMalloc((void**)&c->d_gb_prim, npx * 4));
         HIPC(c, hipMalloc((void**)&c->d_prev_prim, npx * 4));
         HIPC(c, hipMalloc((void**)&c->d_dn_rgba, npx * 4));
+        HIPC(c, hipMalloc((void**)&c->d_dn_var, 3 * npx * sizeof(float)));
         HIPC(c, hipMemsetAsync(c->d_gb_pos, 0, npx * sizeof(float4), c->stream));   // FrameBuffer::Reset value-initializes
         HIPC(c, hipMemsetAsync(c->d_gb_nrm, 0, npx * sizeof(float4), c->stream));
         c->dn_pixels = npx;
         c->have_prev = false;
+        c->svgf_last = false;
     }
     // 1) the G-buffer frame: the megakernel in GB mode, one sample per pixel
     rt_render_params rp{frame, 1u, seed, rr, RT_RENDER_EXACT};
@@ -1303,6 +1307,8 @@ static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float pr
     D.color = c->d_gb_color; D.pos = c->d_gb_pos; D.nrm = c->d_gb_nrm; D.prim = c->d_gb_prim;
     D.spatial = (dp->jbf_half_size > 0 || atrous_levels > 0) ? c->d_spatial : c->d_gb_color;
     D.atrous_levels = atrous_levels; D.scratch = c->d_dn_scratch;
+    D.svgf = sigma_luminance > 0.0f; D.sigma_luminance = sigma_luminance;
+    D.var0 = c->d_dn_var; D.var_a = c->d_dn_var + npx; D.var_b = c->d_dn_var + 2 * npx;
     D.prev_color = c->d_prev_color; D.prev_prim = c->d_prev_prim;
     D.temporal = c->d_temporal; D.rgba = c->d_dn_rgba;
     D.jbf_half = dp->jbf_half_size; D.immediate_clamp = dp->immediate_clamp != 0;
@@ -1315,6 +1321,7 @@ static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float pr
     HIPC(c, rt_launch_denoise(D, c->stream));
     HIPC(c, hipEventRecord(c->ev3, c->stream));
     c->pending_denoise = true;
+    c->svgf_last = D.svgf != 0;
     // the history: previous_frame_g_buffer = g_buffer (its color is the temporal output), DN/Denoiser.h:321-325
     if (temporal) {
         HIPC(c, hipMemcpyAsync(c->d_prev_color, c->d_temporal, npx * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
@@ -1333,7 +1340,7 @@ static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float pr
 rt_status rt_render_denoised(rt_ctx* c, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame, uint64_t seed, float rr,
                              const rt_denoise_params* dp, uint32_t* out_rgba, float* out_color)
 {
-    return render_denoised(c, cam, proj, view, frame, seed, rr, dp, 0, out_rgba, out_color);
+    return render_denoised(c, cam, proj, view, frame, seed, rr, dp, 0, 0.0f, out_rgba, out_color);
 }
 
 rt_status rt_render_denoised_atrous(rt_ctx* c, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame, uint64_t seed,
@@ -1341,7 +1348,28 @@ rt_status rt_render_denoised_atrous(rt_ctx* c, const rt_camera* cam, const float
 {
     if (!c) return RT_ERR_INVALID;
     if (levels < 1 || levels > 8) { c->err = "a-trous levels must be in 1 .. 8"; return RT_ERR_INVALID; }
-    return render_denoised(c, cam, proj, view, frame, seed, rr, dp, levels, out_rgba, out_color);
+    return render_denoised(c, cam, proj, view, frame, seed, rr, dp, levels, 0.0f, out_rgba, out_color);
+}
+
+rt_status rt_render_denoised_svgf(rt_ctx* c, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame, uint64_t seed,
+                                  float rr, const rt_denoise_params* dp, int32_t levels, float sigma_luminance, uint32_t* out_rgba, float* out_color)
+{
+    if (!c) return RT_ERR_INVALID;
+    if (levels < 1 || levels > 8) { c->err = "a-trous levels must be in 1 .. 8"; return RT_ERR_INVALID; }
+    if (!(sigma_luminance > 0.0f) || !std::isfinite(sigma_luminance)) { c->err = "sigma_luminance must be finite and positive"; return RT_ERR_INVALID; }
+    return render_denoised(c, cam, proj, view, frame, seed, rr, dp, levels, sigma_luminance, out_rgba, out_color);
+}
+
+rt_status rt_get_variance(rt_ctx* c, float* var0, float* varL)
+{
+    if (!c) return RT_ERR_INVALID;
+    if (!c->dn_pixels || !c->svgf_last) { c->err = "the last denoised frame was not an rt_render_denoised_svgf one"; return RT_ERR_STATE; }
+    HIPC(c, hipSetDevice(c->device));
+    const size_t n = c->dn_pixels;
+    if (var0) HIPC(c, hipMemcpyAsync(var0, c->d_dn_var, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (varL) HIPC(c, hipMemcpyAsync(varL, c->d_dn_var + n, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
 }
 
 rt_status rt_get_gbuffer(rt_ctx* c, float* color, float* position, float* normal, int32_t* prim, float* spatial)

@@ -301,7 +301,7 @@ hipError_t rt_launch_denoise(const DenoiseParams& D, hipStream_t stream)
     const uint32_t tiles = (uint32_t)(((D.W + 15) / 16) * ((D.H + 15) / 16));
     if (tiles == 0) return hipSuccess;
     if (D.atrous_levels > 0) {
-        const hipError_t e = rt_launch_atrous(D, stream);
+        const hipError_t e = D.svgf ? rt_launch_svgf(D, stream) : rt_launch_atrous(D, stream);
         if (e != hipSuccess) return e;
     } else if (D.jbf_half > 0) {
         DenoiseParams Dl = D;

@@ -170,10 +170,17 @@ struct DenoiseParams {
     // bilateral filter (jbf_half is ignored); its levels ping-pong between `scratch` and `spatial`
     int atrous_levels;
     float4* scratch;
+    // svgf != 0 (with atrous_levels > 0): the levels are the variance-guided ones (rt_svgf.hip); sigma_color is ignored.
+    // W x H floats each: var0 receives the initial variance, the levels' variance ping-pongs between var_a and var_b
+    // and the last level's lands in var_a
+    int svgf; float sigma_luminance;
+    float *var0, *var_a, *var_b;
 };
 hipError_t rt_launch_denoise(const DenoiseParams& D, hipStream_t stream);
 // the a-trous levels alone (D.atrous_levels in 1 .. 8): D.color -> D.spatial (called by rt_launch_denoise)
 hipError_t rt_launch_atrous(const DenoiseParams& D, hipStream_t stream);
+// the moments kernel and the variance-guided levels (D.svgf): D.color -> D.var0, D.spatial, D.var_a (called by rt_launch_denoise)
+hipError_t rt_launch_svgf(const DenoiseParams& D, hipStream_t stream);
 
 // GPU BVH build (rt_lbvh.hip): a Karras LBVH in the traversal layout (rt_layout.h nodes / tris).
 // verts: 9 floats per triangle (a, b, c); recs: the triangle records (4 float4 per triangle); n >= 2.

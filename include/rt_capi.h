@@ -21,6 +21,7 @@
  *   rt_render_denoised                    Denoiser project Renderer::Render (G-buffer, JBF,    DN/Renderer.cpp:101-311,
  *                                         temporal filter)                                   DN/Denoiser.h:133-328
  *   rt_render_denoised_atrous             (no reference counterpart: the same frame with an a-trous wavelet spatial pass)
+ *   rt_render_denoised_svgf, rt_get_variance   (no reference counterpart: the a-trous pass guided by a luminance variance)
  *   rt_scene_add_world_sphere / _mesh     Whitted Style Ray Tracer Sphere / TriangleMesh + World::Add
  *                                         (WH/Sphere.h:16-75, WH/TriangleMesh.h:47-155, WH/World.h:37-45)
  *   rt_scene_add_two_spheres_scene        Whitted Style Ray Tracer Renderer::Renderer()       WH/Renderer.cpp:27-49
@@ -388,6 +389,17 @@ rt_status rt_render_denoised(rt_ctx* ctx, const rt_camera* cam, const float proj
  * frames filtered either way may follow each other. */
 rt_status rt_render_denoised_atrous(rt_ctx* ctx, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame,
                                     uint64_t seed, float rr, const rt_denoise_params* p, int32_t levels, uint32_t* out_rgba, float* out_color);
+/* the same frame with the variance-guided a-trous levels of SVGF's spatial stage (Schied et al. 2017) as the spatial
+ * pass: a per-pixel luminance variance from a 7 x 7 window, then `levels` (1 .. 8) a-trous passes whose color
+ * edge-stop is |lum(q) - lum(p)| / (sigma_luminance sqrt(G3(Var)(p)) + 1e-6) and which filter the variance along with
+ * the color.  p->sigma_color and p->jbf_half_size are ignored; sigma_luminance must be finite and
+ * positive (SVGF's own value is 4).  Everything after the spatial pass is shared with rt_render_denoised. */
+rt_status rt_render_denoised_svgf(rt_ctx* ctx, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame,
+                                  uint64_t seed, float rr, const rt_denoise_params* p, int32_t levels, float sigma_luminance,
+                                  uint32_t* out_rgba, float* out_color);
+/* the last frame's variance planes (W x H floats each; either pointer may be NULL): the initial estimate Var_0 and the
+ * last level's Var_L.  RT_ERR_STATE when the last denoised frame was not an rt_render_denoised_svgf one. */
+rt_status rt_get_variance(rt_ctx* ctx, float* var0, float* varL);
 rt_status rt_denoise_restart(rt_ctx* ctx);
 /* the last denoised frame's buffers (W x H each; any pointer may be NULL): G-buffer color / world
  * position / normal (4 floats per pixel), primitive id (-1: primary ray missed), joint bilateral output */

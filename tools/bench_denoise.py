@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """tools/bench_denoise.py -- the denoiser's spatial + temporal kernels on one GPU, Cornell box at 1920x1080: the joint
-bilateral filter (half sizes 16 and 32) and the a-trous wavelet filter (3, 4, 5 levels), one JSON line each.
+bilateral filter (half sizes 16 and 32), the a-trous wavelet filter (3, 4, 5 levels) and its variance-guided form (SVGF's
+spatial stage, 5 levels, sigma_luminance 4), one JSON line each.
 
 One process; each repeat is one denoised frame with the temporal filter on (half size 3) and the default sigmas, timed by
 the library's HIP events around the filters (rt_stats.last_denoise_ms); warm-up frames of the same case come first.
@@ -14,7 +15,7 @@ import statistics
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(REPO, "cpu-based-ray-tracer_amd")
-CASES = [("jbf", 16), ("jbf", 32), ("atrous", 3), ("atrous", 4), ("atrous", 5)]
+CASES = [("jbf", 16), ("jbf", 32), ("atrous", 3), ("atrous", 4), ("atrous", 5), ("svgf", 5)]
 
 
 def main():
@@ -38,6 +39,8 @@ def main():
         for i in range(a.warmup + a.repeats):
             if kind == "jbf":
                 ctx.render_denoised(cam, proj, view, i + 1, params, seed=1, fetch=False)
+            elif kind == "svgf":
+                ctx.render_denoised_svgf(cam, proj, view, i + 1, params, n, seed=1, fetch=False)
             else:
                 ctx.render_denoised_atrous(cam, proj, view, i + 1, params, n, seed=1, fetch=False)
             st = ctx.stats()   # synchronises with the frame's events
