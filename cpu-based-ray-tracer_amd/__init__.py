@@ -178,6 +178,9 @@ def lib():
         "rt_render_denoised_atrous": (i32, [vp, C.POINTER(Camera), fp, fp, u32, u64, C.c_float, C.POINTER(DenoiseParams), i32, C.POINTER(u32), fp]),
         "rt_render_denoised_svgf": (i32, [vp, C.POINTER(Camera), fp, fp, u32, u64, C.c_float, C.POINTER(DenoiseParams), i32, C.c_float, C.POINTER(u32), fp]),
         "rt_get_variance": (i32, [vp, fp, fp]),
+        "rt_render_denoised_svgf_temporal": (i32, [vp, C.POINTER(Camera), fp, fp, u32, u64, C.c_float, C.POINTER(DenoiseParams), i32, C.c_float,
+                                             C.c_float, C.c_float, C.POINTER(u32), fp]),
+        "rt_get_svgf_history": (i32, [vp, fp, fp, fp]),
         "rt_denoise_restart": (i32, [vp]),
         "rt_get_gbuffer": (i32, [vp, fp, fp, fp, C.POINTER(i32), fp]),
         "rt_scene_add_np_sphere": (i32, [vp, fp, C.c_float, C.POINTER(NpMaterial), C.POINTER(i32)]),
@@ -736,6 +739,28 @@ class Context:
         v0 = np.zeros((self.H, self.W), np.float32); vl = np.zeros((self.H, self.W), np.float32)
         self._check(lib().rt_get_variance(self.h, _fp(v0), _fp(vl)), "rt_get_variance")
         return dict(initial=v0, filtered=vl)
+
+    def render_denoised_svgf_temporal(self, cam, proj, view, frame, params, levels, sigma_luminance=4.0, alpha_color=0.2, alpha_moments=0.2,
+                                      seed=0, rr=0.8, fetch=True):
+        """Full SVGF (csrc/rt_svgf_temporal.hip): color and luminance moments accumulated over the reprojected history of this
+        entry point's earlier frames, then render_denoised_svgf's levels on the accumulated color; the alphas are in (0, 1]."""
+        proj = np.ascontiguousarray(proj, np.float32); view = np.ascontiguousarray(view, np.float32)
+        rgba = np.zeros((self.H, self.W), np.uint32) if fetch else None
+        col = np.zeros((self.H, self.W, 4), np.float32) if fetch else None
+        self._check(lib().rt_render_denoised_svgf_temporal(self.h, C.byref(cam), _fp(proj), _fp(view), frame, seed, rr, C.byref(params), levels,
+                                                           sigma_luminance, alpha_color, alpha_moments,
+                                                           rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if fetch else None,
+                                                           _fp(col) if fetch else None), "rt_render_denoised_svgf_temporal")
+        return (rgba, col) if fetch else None
+
+    def svgf_history(self):
+        """The state after the last render_denoised_svgf_temporal frame: the color the next frame reprojects, the luminance
+        moments, the history length, the primitive ids and that frame's accumulated color."""
+        n = (self.H, self.W, 4)
+        hist = np.zeros(n, np.float32); m = np.zeros(n, np.float32); ci = np.zeros(n, np.float32)
+        self._check(lib().rt_get_svgf_history(self.h, _fp(hist), _fp(m), _fp(ci)), "rt_get_svgf_history")
+        return dict(hist_color=hist, mu1=m[..., 0], mu2=m[..., 1], length=m[..., 2], prim=np.ascontiguousarray(m[..., 3]).view(np.int32),
+                    integrated=ci)
 
     def denoise_restart(self):
         self._check(lib().rt_denoise_restart(self.h), "rt_denoise_restart")

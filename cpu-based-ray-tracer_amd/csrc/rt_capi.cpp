@@ -93,6 +93,13 @@ struct rt_ctx {
     float4 *d_dn_scratch = nullptr;   // the a-trous filter's second level buffer
     float *d_dn_var = nullptr;        // rt_render_denoised_svgf: three W x H planes (Var_0, Var_L, the levels' other buffer)
     bool svgf_last = false;           // the last denoised frame was an SVGF one (rt_get_variance)
+    // rt_render_denoised_svgf_temporal: H_c, C_int and M in two planes that alternate by frame (svgf_m_cur: the last M');
+    // a history of its own, apart from prev_color / prev_prim
+    float4 *d_svgf_hist = nullptr, *d_svgf_cint = nullptr, *d_svgf_m[2] = {nullptr, nullptr};
+    int svgf_m_cur = 0;
+    bool svgf_have_hist = false;      // the next frame of this kind may reproject
+    bool svgft_last = false;          // the last denoised frame was of this kind (rt_get_svgf_history)
+    float svgf_prev_proj[16] = {}, svgf_prev_view[16] = {};
     size_t dn_pixels = 0;
     bool have_prev = false;
     float prev_proj[16] = {}, prev_view[16] = {};
@@ -608,6 +615,7 @@ void rt_destroy(rt_ctx* c)
     dfree(c->d_went); dfree(c->d_wtris); dfree(c->d_np);
     dfree(c->d_gb_color); dfree(c->d_gb_pos); dfree(c->d_gb_nrm); dfree(c->d_spatial); dfree(c->d_temporal); dfree(c->d_prev_color);
     dfree(c->d_gb_prim); dfree(c->d_prev_prim); dfree(c->d_dn_rgba); dfree(c->d_dn_scratch); dfree(c->d_dn_var); dfree(c->d_lbuf); dfree(c->d_sky);
+    dfree(c->d_svgf_hist); dfree(c->d_svgf_cint); dfree(c->d_svgf_m[0]); dfree(c->d_svgf_m[1]);
     dfree(c->d_crec); dfree(c->d_seg_list); dfree(c->d_tile_boxes);
     if (c->ev2) (void)hipEventDestroy(c->ev2);
     if (c->ev3) (void)hipEventDestroy(c->ev3);
@@ -1259,13 +1267,16 @@ rt_status rt_denoise_restart(rt_ctx* c)
 {
     if (!c) return RT_ERR_INVALID;
     c->have_prev = false;
+    c->svgf_have_hist = false;
     return RT_OK;
 }
 
 // one denoised frame; atrous_levels > 0: the a-trous wavelet filter is the spatial pass (rt_atrous.hip), variance-guided
-// (rt_svgf.hip) when sigma_luminance > 0; else the joint bilateral filter
+// (rt_svgf.hip) when sigma_luminance > 0; else the joint bilateral filter.  alphas (alpha_color, alpha_moments) != nullptr:
+// full SVGF (rt_svgf_temporal.hip) -- its own history in front of the levels, the reference's temporal filter off
 static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame, uint64_t seed, float rr,
-                                 const rt_denoise_params* dp, int atrous_levels, float sigma_luminance, uint32_t* out_rgba, float* out_color)
+                                 const rt_denoise_params* dp, int atrous_levels, float sigma_luminance, uint32_t* out_rgba, float* out_color,
+                                 const float* alphas = nullptr)
 {
     if (!c || !cam || !proj || !view || !dp) return RT_ERR_INVALID;
     if (!c->has_scene || c->hdr.n_nodes == 0) { c->err = "no triangle scene uploaded"; return RT_ERR_STATE; }
@@ -1281,7 +1292,9 @@ static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float pr
         HIPC(c, hipStreamSynchronize(c->stream));
         dfree(c->d_gb_color); dfree(c->d_gb_pos); dfree(c->d_gb_nrm); dfree(c->d_spatial); dfree(c->d_temporal); dfree(c->d_prev_color);
         dfree(c->d_gb_prim); dfree(c->d_prev_prim); dfree(c->d_dn_rgba); dfree(c->d_dn_scratch); dfree(c->d_dn_var);
-        float4** f4[7] = {&c->d_gb_color, &c->d_gb_pos, &c->d_gb_nrm, &c->d_spatial, &c->d_temporal, &c->d_prev_color, &c->d_dn_scratch};
+        dfree(c->d_svgf_hist); dfree(c->d_svgf_cint); dfree(c->d_svgf_m[0]); dfree(c->d_svgf_m[1]);
+        float4** f4[11] = {&c->d_gb_color, &c->d_gb_pos, &c->d_gb_nrm, &c->d_spatial, &c->d_temporal, &c->d_prev_color, &c->d_dn_scratch,
+                           &c->d_svgf_hist, &c->d_svgf_cint, &c->d_svgf_m[0], &c->d_svgf_m[1]};
         for (float4** q : f4) HIPC(c, hipMalloc((void**)q, npx * sizeof(float4)));
         HIPC(c, hipMalloc((void**)&c->d_gb_prim, npx * 4));
         HIPC(c, hipMalloc((void**)&c->d_prev_prim, npx * 4));
@@ -1292,6 +1305,8 @@ static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float pr
         c->dn_pixels = npx;
         c->have_prev = false;
         c->svgf_last = false;
+        c->svgf_have_hist = false;
+        c->svgft_last = false;
     }
     // 1) the G-buffer frame: the megakernel in GB mode, one sample per pixel
     rt_render_params rp{frame, 1u, seed, rr, RT_RENDER_EXACT};
@@ -1301,7 +1316,7 @@ static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float pr
     c->gb_next = false;
     if (st != RT_OK) return st;
     // 2) joint bilateral or a-trous levels + 3) temporal (+ pack)
-    const bool temporal = dp->temporal_half_size > 0;
+    const bool temporal = !alphas && dp->temporal_half_size > 0;   // (full SVGF ignores temporal_half_size: the pack runs without a history)
     DenoiseParams D{};
     D.W = (int)c->W; D.H = (int)c->H;
     D.color = c->d_gb_color; D.pos = c->d_gb_pos; D.nrm = c->d_gb_nrm; D.prim = c->d_gb_prim;
@@ -1317,11 +1332,26 @@ static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float pr
     D.have_prev = temporal && c->have_prev;
     std::memcpy(D.prev_proj, c->prev_proj, sizeof D.prev_proj);
     std::memcpy(D.prev_view, c->prev_view, sizeof D.prev_view);
+    SvgfTemporalParams T{};
+    if (alphas) {
+        T.hist = c->d_svgf_hist; T.integrated = c->d_svgf_cint;
+        T.m_prev = c->d_svgf_m[c->svgf_m_cur]; T.m_next = c->d_svgf_m[c->svgf_m_cur ^ 1];
+        T.have_hist = c->svgf_have_hist; T.alpha_color = alphas[0]; T.alpha_moments = alphas[1];
+        std::memcpy(T.prev_proj, c->svgf_prev_proj, sizeof T.prev_proj);
+        std::memcpy(T.prev_view, c->svgf_prev_view, sizeof T.prev_view);
+    }
     HIPC(c, hipEventRecord(c->ev2, c->stream));
-    HIPC(c, rt_launch_denoise(D, c->stream));
+    HIPC(c, rt_launch_denoise(D, c->stream, alphas ? &T : nullptr));
     HIPC(c, hipEventRecord(c->ev3, c->stream));
     c->pending_denoise = true;
     c->svgf_last = D.svgf != 0;
+    // SVGF's history: M' becomes M, level 0 has left C_1 in d_svgf_hist; a frame of another kind drops it
+    c->svgft_last = c->svgf_have_hist = alphas != nullptr;
+    if (alphas) {
+        c->svgf_m_cur ^= 1;
+        std::memcpy(c->svgf_prev_proj, proj, sizeof c->svgf_prev_proj);
+        std::memcpy(c->svgf_prev_view, view, sizeof c->svgf_prev_view);
+    }
     // the history: previous_frame_g_buffer = g_buffer (its color is the temporal output), DN/Denoiser.h:321-325
     if (temporal) {
         HIPC(c, hipMemcpyAsync(c->d_prev_color, c->d_temporal, npx * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
@@ -1358,6 +1388,32 @@ rt_status rt_render_denoised_svgf(rt_ctx* c, const rt_camera* cam, const float p
     if (levels < 1 || levels > 8) { c->err = "a-trous levels must be in 1 .. 8"; return RT_ERR_INVALID; }
     if (!(sigma_luminance > 0.0f) || !std::isfinite(sigma_luminance)) { c->err = "sigma_luminance must be finite and positive"; return RT_ERR_INVALID; }
     return render_denoised(c, cam, proj, view, frame, seed, rr, dp, levels, sigma_luminance, out_rgba, out_color);
+}
+
+rt_status rt_render_denoised_svgf_temporal(rt_ctx* c, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame,
+                                           uint64_t seed, float rr, const rt_denoise_params* dp, int32_t levels, float sigma_luminance,
+                                           float alpha_color, float alpha_moments, uint32_t* out_rgba, float* out_color)
+{
+    if (!c) return RT_ERR_INVALID;
+    if (levels < 1 || levels > 8) { c->err = "a-trous levels must be in 1 .. 8"; return RT_ERR_INVALID; }
+    if (!(sigma_luminance > 0.0f) || !std::isfinite(sigma_luminance)) { c->err = "sigma_luminance must be finite and positive"; return RT_ERR_INVALID; }
+    const float alphas[2] = {alpha_color, alpha_moments};
+    for (float a : alphas)
+        if (!(a > 0.0f && a <= 1.0f)) { c->err = "alpha_color and alpha_moments must be in (0, 1]"; return RT_ERR_INVALID; }
+    return render_denoised(c, cam, proj, view, frame, seed, rr, dp, levels, sigma_luminance, out_rgba, out_color, alphas);
+}
+
+rt_status rt_get_svgf_history(rt_ctx* c, float* hist_color, float* moments, float* integrated)
+{
+    if (!c) return RT_ERR_INVALID;
+    if (!c->dn_pixels || !c->svgft_last) { c->err = "the last denoised frame was not an rt_render_denoised_svgf_temporal one"; return RT_ERR_STATE; }
+    HIPC(c, hipSetDevice(c->device));
+    const size_t n = c->dn_pixels * sizeof(float4);
+    if (hist_color) HIPC(c, hipMemcpyAsync(hist_color, c->d_svgf_hist, n, hipMemcpyDeviceToHost, c->stream));
+    if (moments) HIPC(c, hipMemcpyAsync(moments, c->d_svgf_m[c->svgf_m_cur], n, hipMemcpyDeviceToHost, c->stream));
+    if (integrated) HIPC(c, hipMemcpyAsync(integrated, c->d_svgf_cint, n, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
 }
 
 rt_status rt_get_variance(rt_ctx* c, float* var0, float* varL)

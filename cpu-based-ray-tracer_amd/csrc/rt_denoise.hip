@@ -296,12 +296,13 @@ __global__ void __launch_bounds__(256) temporal_kernel(DenoiseParams D)
     D.rgba[i] = (to_u8(1.0f) << 24) | (to_u8(b) << 16) | (to_u8(g) << 8) | to_u8(r);
 }
 
-hipError_t rt_launch_denoise(const DenoiseParams& D, hipStream_t stream)
+hipError_t rt_launch_denoise(const DenoiseParams& D, hipStream_t stream, const SvgfTemporalParams* T)
 {
     const uint32_t tiles = (uint32_t)(((D.W + 15) / 16) * ((D.H + 15) / 16));
     if (tiles == 0) return hipSuccess;
+    if (T && !(D.atrous_levels > 0 && D.svgf && !D.have_prev)) return hipErrorInvalidValue;
     if (D.atrous_levels > 0) {
-        const hipError_t e = D.svgf ? rt_launch_svgf(D, stream) : rt_launch_atrous(D, stream);
+        const hipError_t e = D.svgf ? rt_launch_svgf(D, stream, T) : rt_launch_atrous(D, stream);
         if (e != hipSuccess) return e;
     } else if (D.jbf_half > 0) {
         DenoiseParams Dl = D;

@@ -176,11 +176,25 @@ struct DenoiseParams {
     int svgf; float sigma_luminance;
     float *var0, *var_a, *var_b;
 };
-hipError_t rt_launch_denoise(const DenoiseParams& D, hipStream_t stream);
+// SVGF's temporal accumulation in front of the variance-guided levels (rt_svgf_temporal.hip); W x H float4 each
+struct SvgfTemporalParams {
+    float4* hist;             // H_c: read by the reprojection (when have_hist), then overwritten with C_1 by level 0
+    float4* integrated;       // C_int, the levels' input
+    const float4* m_prev;     // M of the previous frame: (mu1, mu2, history length, bits of the primitive id)
+    float4* m_next;           // M' (never m_prev: a lane reads its neighbours' old values)
+    int have_hist;
+    float alpha_color, alpha_moments;
+    float prev_proj[16], prev_view[16];   // the history's camera
+};
+// T != nullptr (with D.svgf): the levels run on the accumulated color and the temporal variance; D.have_prev must be 0
+hipError_t rt_launch_denoise(const DenoiseParams& D, hipStream_t stream, const SvgfTemporalParams* T = nullptr);
 // the a-trous levels alone (D.atrous_levels in 1 .. 8): D.color -> D.spatial (called by rt_launch_denoise)
 hipError_t rt_launch_atrous(const DenoiseParams& D, hipStream_t stream);
-// the moments kernel and the variance-guided levels (D.svgf): D.color -> D.var0, D.spatial, D.var_a (called by rt_launch_denoise)
-hipError_t rt_launch_svgf(const DenoiseParams& D, hipStream_t stream);
+// the moments kernel and the variance-guided levels (D.svgf): D.color -> D.var0, D.spatial, D.var_a (called by rt_launch_denoise);
+// with T, stages R and V of 5.9 replace the moments kernel and level 0 leaves C_1 in T->hist
+hipError_t rt_launch_svgf(const DenoiseParams& D, hipStream_t stream, const SvgfTemporalParams* T = nullptr);
+// stages R and V: svgf_reproject_kernel, svgf_variance_kernel -> T.integrated, T.m_next, D.var0 (called by rt_launch_svgf)
+hipError_t rt_launch_svgf_accumulate(const DenoiseParams& D, const SvgfTemporalParams& T, hipStream_t stream);
 
 // GPU BVH build (rt_lbvh.hip): a Karras LBVH in the traversal layout (rt_layout.h nodes / tris).
 // verts: 9 floats per triangle (a, b, c); recs: the triangle records (4 float4 per triangle); n >= 2.

@@ -6,6 +6,8 @@
 // Levels (svgf_kernel<DC, DR>): rt_atrous.hip's 5 x 5 B3-spline levels, the color edge-stop replaced by
 // |lum(q) - lum(p)| / (sigma_l sqrt(G3(Var)(p)) + eps), the variance filtered along with the color by the squared
 // weights.  One launch per level; color ping-pongs as in rt_launch_atrous, variance in fp32 planes of its own.
+// With a SvgfTemporalParams (rt_render_denoised_svgf_temporal) rt_svgf_temporal.hip's two kernels take stage
+// V's place and the levels run on the accumulated color; level 0 then writes the next frame's history.
 // Like rt_atrous.hip this path has no CPU original: v_exp_f32 on a host-prescaled exponent, v_rcp_f32, v_rsq_f32,
 // v_sqrt_f32, the short acos, fma contraction on.
 //
@@ -29,10 +31,7 @@
 
 namespace {
 
-constexpr int MO_HALO = 3, MO_TC = AT_BW + 2 * MO_HALO, MO_TR = AT_BH + 2 * MO_HALO;   // 38 x 14 cells
-constexpr int MO_PITCH = 160, MO_SLOT = 40, MO_SET = MO_TR * MO_PITCH;                 // 7 planes in 2 row-sets of four
-static_assert(MO_TC <= MO_SLOT && 4 * MO_SLOT <= MO_PITCH && MO_PITCH % 64 == 32, "four planes share a row; rows 32 banks apart");
-constexpr float SVGF_EPS = 1e-6f, L2E = 1.4426950408889634f;
+constexpr float SVGF_EPS = 1e-6f, L2E = 1.4426950408889634f;   // (the moments tile, lum and geo_log2: rt_atrous_tile.h)
 
 struct SvgfLevel {
     int W, H;
@@ -45,21 +44,6 @@ struct SvgfLevel {
     float ep, en, ek;                // -log2(e) / (2 sigma^2): the geometry weight is exp2 of the weighted sum
     float sl;                        // sigma_luminance
 };
-
-__device__ __forceinline__ float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
-
-// log2 of the three geometry edge-stops between the centre (position p, normal n) and a tap (position difference
-// d, normal m): rt_atrous.hip's terms without the color distance
-__device__ __forceinline__ float geo_log2(float nx, float ny, float nz, float dx, float dy, float dz, float mx, float my, float mz,
-                                          float ep, float en, float ek)
-{
-    const float xp = dx * dx + dy * dy + dz * dz;
-    const float an = acos_unit(fminf(fmaxf(mx * nx + my * ny + mz * nz, 0.0f), 1.0f));
-    // N_p . normalize(P_q - P_p); points closer than 2^-50 count as the same point (term 0)
-    const float cp = (nx * dx + ny * dy + nz * dz) * __builtin_amdgcn_rsqf(xp);
-    const float cop = xp >= 0x1p-100f ? cp * cp : 0.0f;
-    return xp * ep + an * an * en + cop * ek;
-}
 
 // stage V: Var_0 of every pixel (A.src: the G-buffer color, A.vdst: Var_0; step, clamp, sl, vsrc, dst unused)
 __global__ void __launch_bounds__(256) moments_kernel(SvgfLevel A)
@@ -254,11 +238,12 @@ __global__ void __launch_bounds__(256) svgf_kernel(SvgfLevel A)
 
 }  // namespace
 
-hipError_t rt_launch_svgf(const DenoiseParams& D, hipStream_t stream)
+hipError_t rt_launch_svgf(const DenoiseParams& D, hipStream_t stream, const SvgfTemporalParams* T)
 {
     const int L = D.atrous_levels;
     if (L < 1 || L > 8 || !D.scratch || !D.var0 || !D.var_a || !D.var_b || !(D.sigma_luminance > 0.0f) || D.W <= 0 || D.H <= 0)
         return hipErrorInvalidValue;
+    if (T && (!T->hist || !T->integrated || !T->m_prev || !T->m_next)) return hipErrorInvalidValue;
     SvgfLevel A{};
     A.W = D.W; A.H = D.H; A.pos = D.pos; A.nrm = D.nrm; A.prim = D.prim;
     const double l2e = 1.4426950408889634;
@@ -266,17 +251,24 @@ hipError_t rt_launch_svgf(const DenoiseParams& D, hipStream_t stream)
     A.ep = coef(D.sigma_position); A.en = coef(D.sigma_normal); A.ek = coef(D.sigma_coplanarity);
     A.sl = D.sigma_luminance;
     const uint32_t blocks = (uint32_t)((D.W + AT_BW - 1) / AT_BW) * (uint32_t)((D.H + AT_BH - 1) / AT_BH);
-    // stage V: the G-buffer color -> Var_0
-    A.src = D.color; A.vdst = D.var0;
-    hipLaunchKernelGGL(moments_kernel, dim3(blocks), dim3(256), 0, stream, A);
-    hipError_t e = hipGetLastError();
+    hipError_t e;
+    if (T) {
+        // stages R and V of the temporal form (rt_svgf_temporal.hip): the G-buffer and the history -> C_int, M', Var_0
+        e = rt_launch_svgf_accumulate(D, *T, stream);
+    } else {
+        // stage V: the G-buffer color -> Var_0
+        A.src = D.color; A.vdst = D.var0;
+        hipLaunchKernelGGL(moments_kernel, dim3(blocks), dim3(256), 0, stream, A);
+        e = hipGetLastError();
+    }
     if (e != hipSuccess) return e;
-    const float4* src = D.color;
+    const float4* src = T ? T->integrated : D.color;
     const float* vsrc = D.var0;
     for (int l = 0; l < L; ++l) {
-        // ping-pong so that the last level lands in D.spatial and D.var_a; Var_0 stays in D.var0
+        // ping-pong so that the last level lands in D.spatial and D.var_a; Var_0 stays in D.var0.  The temporal form's
+        // level 0 writes the next frame's history H_c = C_1 (stage R has read the old one); no later level writes it
         const bool odd = (L - 1 - l) & 1;
-        float4* dst = odd ? D.scratch : D.spatial;
+        float4* dst = T && l == 0 ? T->hist : odd ? D.scratch : D.spatial;
         float* vdst = odd ? D.var_b : D.var_a;
         const int s = 1 << l;
         A.src = src; A.dst = dst; A.vsrc = vsrc; A.vdst = vdst; A.step = s;
@@ -293,5 +285,7 @@ hipError_t rt_launch_svgf(const DenoiseParams& D, hipStream_t stream)
         if (e != hipSuccess) return e;
         src = dst; vsrc = vdst;
     }
+    // one level: C_1 is the history and the output
+    if (T && L == 1) return hipMemcpyAsync(D.spatial, T->hist, (size_t)D.W * D.H * sizeof(float4), hipMemcpyDeviceToDevice, stream);
     return hipSuccess;
 }

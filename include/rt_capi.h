@@ -22,6 +22,8 @@
  *                                         temporal filter)                                   DN/Denoiser.h:133-328
  *   rt_render_denoised_atrous             (no reference counterpart: the same frame with an a-trous wavelet spatial pass)
  *   rt_render_denoised_svgf, rt_get_variance   (no reference counterpart: the a-trous pass guided by a luminance variance)
+ *   rt_render_denoised_svgf_temporal, rt_get_svgf_history   (no reference counterpart: full SVGF, that pass behind a
+ *                                         temporal accumulation of color and luminance moments)
  *   rt_scene_add_world_sphere / _mesh     Whitted Style Ray Tracer Sphere / TriangleMesh + World::Add
  *                                         (WH/Sphere.h:16-75, WH/TriangleMesh.h:47-155, WH/World.h:37-45)
  *   rt_scene_add_two_spheres_scene        Whitted Style Ray Tracer Renderer::Renderer()       WH/Renderer.cpp:27-49
@@ -400,6 +402,23 @@ rt_status rt_render_denoised_svgf(rt_ctx* ctx, const rt_camera* cam, const float
 /* the last frame's variance planes (W x H floats each; either pointer may be NULL): the initial estimate Var_0 and the
  * last level's Var_L.  RT_ERR_STATE when the last denoised frame was not an rt_render_denoised_svgf one. */
 rt_status rt_get_variance(rt_ctx* ctx, float* var0, float* varL);
+/* full SVGF: temporal accumulation in front of rt_render_denoised_svgf's levels.  Each contributor is
+ * reprojected with the previous frame's proj and view; the history pixels of the same primitive around that point blend
+ * bilinearly, and the color and the first two luminance moments are accumulated with the weights max(alpha_color,
+ * 1 / history length) and max(alpha_moments, 1 / history length).  The variance is mu2 - mu1^2 from a history of four
+ * frames on and a 7 x 7 window of the moments before; the levels filter the accumulated color, the first level's output
+ * is the next frame's history.  levels and sigma_luminance as in rt_render_denoised_svgf; both alphas finite and in
+ * (0, 1] (SVGF's own value is 0.2).  p->temporal_half_size, tolerance, current_frame_weighting, sigma_color and
+ * jbf_half_size are ignored.  The history is this entry point's own: rt_denoise_restart, a change of resolution or a
+ * denoised frame of another kind drops it, and a frame of this kind drops rt_render_denoised's.  rt_get_variance works
+ * after such a frame; out_color is the last level's output (rt_get_gbuffer's spatial, bit for bit). */
+rt_status rt_render_denoised_svgf_temporal(rt_ctx* ctx, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame,
+                                           uint64_t seed, float rr, const rt_denoise_params* p, int32_t levels, float sigma_luminance,
+                                           float alpha_color, float alpha_moments, uint32_t* out_rgba, float* out_color);
+/* the state after the last rt_render_denoised_svgf_temporal frame (W x H x 4 floats each; any pointer may be NULL):
+ * the color the next frame will reproject, the moments (mu1, mu2, history length, the primitive id as the bits of an
+ * int32) and that frame's accumulated color.  RT_ERR_STATE when the last denoised frame was not of that kind. */
+rt_status rt_get_svgf_history(rt_ctx* ctx, float* hist_color, float* moments, float* integrated);
 rt_status rt_denoise_restart(rt_ctx* ctx);
 /* the last denoised frame's buffers (W x H each; any pointer may be NULL): G-buffer color / world
  * position / normal (4 floats per pixel), primitive id (-1: primary ray missed), joint bilateral output */
