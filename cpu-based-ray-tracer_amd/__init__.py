@@ -181,6 +181,9 @@ def lib():
         "rt_render_denoised_svgf_temporal": (i32, [vp, C.POINTER(Camera), fp, fp, u32, u64, C.c_float, C.POINTER(DenoiseParams), i32, C.c_float,
                                              C.c_float, C.c_float, C.POINTER(u32), fp]),
         "rt_get_svgf_history": (i32, [vp, fp, fp, fp]),
+        "rt_render_denoised_svgf_clamped": (i32, [vp, C.POINTER(Camera), fp, fp, u32, u64, C.c_float, C.POINTER(DenoiseParams), i32, C.c_float,
+                                            C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(u32), fp]),
+        "rt_get_svgf_fast_history": (i32, [vp, fp]),
         "rt_denoise_restart": (i32, [vp]),
         "rt_get_gbuffer": (i32, [vp, fp, fp, fp, C.POINTER(i32), fp]),
         "rt_scene_add_np_sphere": (i32, [vp, fp, C.c_float, C.POINTER(NpMaterial), C.POINTER(i32)]),
@@ -753,8 +756,28 @@ class Context:
                                                            _fp(col) if fetch else None), "rt_render_denoised_svgf_temporal")
         return (rgba, col) if fetch else None
 
+    def render_denoised_svgf_clamped(self, cam, proj, view, frame, params, levels, sigma_luminance=4.0, alpha_color=0.2, alpha_moments=0.2,
+                                     alpha_fast=0.5, clamp_sigma=2.0, seed=0, rr=0.8, fetch=True):
+        """render_denoised_svgf_temporal with a fast-history clamp (csrc/rt_svgf_clamp.hip): a second history accumulated with
+        alpha_fast in (0, 1]; the accumulated color is clamped, per channel, to mean +- clamp_sigma (>= 0) standard deviations
+        of that history's 5 x 5 neighbourhood before the levels.  A history of its own, apart from render_denoised_svgf_temporal's."""
+        proj = np.ascontiguousarray(proj, np.float32); view = np.ascontiguousarray(view, np.float32)
+        rgba = np.zeros((self.H, self.W), np.uint32) if fetch else None
+        col = np.zeros((self.H, self.W, 4), np.float32) if fetch else None
+        self._check(lib().rt_render_denoised_svgf_clamped(self.h, C.byref(cam), _fp(proj), _fp(view), frame, seed, rr, C.byref(params), levels,
+                                                          sigma_luminance, alpha_color, alpha_moments, alpha_fast, clamp_sigma,
+                                                          rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if fetch else None,
+                                                          _fp(col) if fetch else None), "rt_render_denoised_svgf_clamped")
+        return (rgba, col) if fetch else None
+
+    def svgf_fast_history(self):
+        """The fast history after the last render_denoised_svgf_clamped frame: its color and the primitive ids."""
+        f = np.zeros((self.H, self.W, 4), np.float32)
+        self._check(lib().rt_get_svgf_fast_history(self.h, _fp(f)), "rt_get_svgf_fast_history")
+        return dict(fast=f, prim=np.ascontiguousarray(f[..., 3]).view(np.int32))
+
     def svgf_history(self):
-        """The state after the last render_denoised_svgf_temporal frame: the color the next frame reprojects, the luminance
+        """The state after the last render_denoised_svgf_temporal (or _clamped) frame: the color the next frame reprojects, the luminance
         moments, the history length, the primitive ids and that frame's accumulated color."""
         n = (self.H, self.W, 4)
         hist = np.zeros(n, np.float32); m = np.zeros(n, np.float32); ci = np.zeros(n, np.float32)

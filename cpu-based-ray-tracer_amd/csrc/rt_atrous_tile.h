@@ -26,6 +26,12 @@ constexpr int MO_HALO = 3, MO_TC = AT_BW + 2 * MO_HALO, MO_TR = AT_BH + 2 * MO_H
 constexpr int MO_PITCH = 160, MO_SLOT = 40, MO_SET = MO_TR * MO_PITCH;
 static_assert(MO_TC <= MO_SLOT && 4 * MO_SLOT <= MO_PITCH && MO_PITCH % 64 == 32, "four planes share a row; rows 32 banks apart");
 
+// the 5 x 5 window's tile (rt_svgf_clamp.hip svgf_clamp_kernel): 36 x 12 cells (halo 2), three fp32 planes per LDS row of
+// CL_PITCH words, plane f at word CL_SLOT f
+constexpr int CL_HALO = 2, CL_TC = AT_BW + 2 * CL_HALO, CL_TR = AT_BH + 2 * CL_HALO;
+constexpr int CL_PITCH = 160, CL_SLOT = 40;
+static_assert(CL_TC <= CL_SLOT && 3 * CL_SLOT <= CL_PITCH && CL_PITCH % 64 == 32, "three planes share a row; rows 32 banks apart");
+
 __device__ __forceinline__ float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
 
 // log2 of the three geometry edge-stops between the centre (position p, normal n) and a tap (position difference

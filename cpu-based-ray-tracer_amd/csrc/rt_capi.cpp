@@ -100,6 +100,10 @@ struct rt_ctx {
     bool svgf_have_hist = false;      // the next frame of this kind may reproject
     bool svgft_last = false;          // the last denoised frame was of this kind (rt_get_svgf_history)
     float svgf_prev_proj[16] = {}, svgf_prev_view[16] = {};
+    // rt_render_denoised_svgf_clamped: the fast history F in two planes that alternate with M's (allocated by the first
+    // frame of that kind); such a frame and a plain rt_render_denoised_svgf_temporal one do not continue each other
+    float4 *d_svgf_fast[2] = {nullptr, nullptr};
+    bool svgfc_last = false;          // the last denoised frame was of that kind (rt_get_svgf_fast_history)
     size_t dn_pixels = 0;
     bool have_prev = false;
     float prev_proj[16] = {}, prev_view[16] = {};
@@ -616,6 +620,7 @@ void rt_destroy(rt_ctx* c)
     dfree(c->d_gb_color); dfree(c->d_gb_pos); dfree(c->d_gb_nrm); dfree(c->d_spatial); dfree(c->d_temporal); dfree(c->d_prev_color);
     dfree(c->d_gb_prim); dfree(c->d_prev_prim); dfree(c->d_dn_rgba); dfree(c->d_dn_scratch); dfree(c->d_dn_var); dfree(c->d_lbuf); dfree(c->d_sky);
     dfree(c->d_svgf_hist); dfree(c->d_svgf_cint); dfree(c->d_svgf_m[0]); dfree(c->d_svgf_m[1]);
+    dfree(c->d_svgf_fast[0]); dfree(c->d_svgf_fast[1]);
     dfree(c->d_crec); dfree(c->d_seg_list); dfree(c->d_tile_boxes);
     if (c->ev2) (void)hipEventDestroy(c->ev2);
     if (c->ev3) (void)hipEventDestroy(c->ev3);
@@ -1273,10 +1278,11 @@ rt_status rt_denoise_restart(rt_ctx* c)
 
 // one denoised frame; atrous_levels > 0: the a-trous wavelet filter is the spatial pass (rt_atrous.hip), variance-guided
 // (rt_svgf.hip) when sigma_luminance > 0; else the joint bilateral filter.  alphas (alpha_color, alpha_moments) != nullptr:
-// full SVGF (rt_svgf_temporal.hip) -- its own history in front of the levels, the reference's temporal filter off
+// full SVGF (rt_svgf_temporal.hip) -- its own history in front of the levels, the reference's temporal filter off; with
+// fast (alpha_fast, clamp_sigma) != nullptr as well, the fast-history clamp between the two (rt_svgf_clamp.hip)
 static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame, uint64_t seed, float rr,
                                  const rt_denoise_params* dp, int atrous_levels, float sigma_luminance, uint32_t* out_rgba, float* out_color,
-                                 const float* alphas = nullptr)
+                                 const float* alphas = nullptr, const float* fast = nullptr)
 {
     if (!c || !cam || !proj || !view || !dp) return RT_ERR_INVALID;
     if (!c->has_scene || c->hdr.n_nodes == 0) { c->err = "no triangle scene uploaded"; return RT_ERR_STATE; }
@@ -1293,6 +1299,7 @@ static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float pr
         dfree(c->d_gb_color); dfree(c->d_gb_pos); dfree(c->d_gb_nrm); dfree(c->d_spatial); dfree(c->d_temporal); dfree(c->d_prev_color);
         dfree(c->d_gb_prim); dfree(c->d_prev_prim); dfree(c->d_dn_rgba); dfree(c->d_dn_scratch); dfree(c->d_dn_var);
         dfree(c->d_svgf_hist); dfree(c->d_svgf_cint); dfree(c->d_svgf_m[0]); dfree(c->d_svgf_m[1]);
+        dfree(c->d_svgf_fast[0]); dfree(c->d_svgf_fast[1]);
         float4** f4[11] = {&c->d_gb_color, &c->d_gb_pos, &c->d_gb_nrm, &c->d_spatial, &c->d_temporal, &c->d_prev_color, &c->d_dn_scratch,
                            &c->d_svgf_hist, &c->d_svgf_cint, &c->d_svgf_m[0], &c->d_svgf_m[1]};
         for (float4** q : f4) HIPC(c, hipMalloc((void**)q, npx * sizeof(float4)));
@@ -1307,7 +1314,10 @@ static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float pr
         c->svgf_last = false;
         c->svgf_have_hist = false;
         c->svgft_last = false;
+        c->svgfc_last = false;
     }
+    for (float4*& q : c->d_svgf_fast)   // the first frame of this kind (at this resolution)
+        if (fast && !q) HIPC(c, hipMalloc((void**)&q, npx * sizeof(float4)));
     // 1) the G-buffer frame: the megakernel in GB mode, one sample per pixel
     rt_render_params rp{frame, 1u, seed, rr, RT_RENDER_EXACT};
     c->gb_next = true;
@@ -1336,9 +1346,15 @@ static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float pr
     if (alphas) {
         T.hist = c->d_svgf_hist; T.integrated = c->d_svgf_cint;
         T.m_prev = c->d_svgf_m[c->svgf_m_cur]; T.m_next = c->d_svgf_m[c->svgf_m_cur ^ 1];
-        T.have_hist = c->svgf_have_hist; T.alpha_color = alphas[0]; T.alpha_moments = alphas[1];
+        // (a plain full-SVGF frame and a clamped one do not continue each other: the other kind's frame left no F, or a
+        // history the clamp never saw)
+        T.have_hist = c->svgf_have_hist && c->svgfc_last == (fast != nullptr); T.alpha_color = alphas[0]; T.alpha_moments = alphas[1];
         std::memcpy(T.prev_proj, c->svgf_prev_proj, sizeof T.prev_proj);
         std::memcpy(T.prev_view, c->svgf_prev_view, sizeof T.prev_view);
+        if (fast) {
+            T.fast_prev = c->d_svgf_fast[c->svgf_m_cur]; T.fast_next = c->d_svgf_fast[c->svgf_m_cur ^ 1];
+            T.alpha_fast = fast[0]; T.clamp_sigma = fast[1];
+        }
     }
     HIPC(c, hipEventRecord(c->ev2, c->stream));
     HIPC(c, rt_launch_denoise(D, c->stream, alphas ? &T : nullptr));
@@ -1347,6 +1363,7 @@ static rt_status render_denoised(rt_ctx* c, const rt_camera* cam, const float pr
     c->svgf_last = D.svgf != 0;
     // SVGF's history: M' becomes M, level 0 has left C_1 in d_svgf_hist; a frame of another kind drops it
     c->svgft_last = c->svgf_have_hist = alphas != nullptr;
+    c->svgfc_last = fast != nullptr;
     if (alphas) {
         c->svgf_m_cur ^= 1;
         std::memcpy(c->svgf_prev_proj, proj, sizeof c->svgf_prev_proj);
@@ -1403,10 +1420,36 @@ rt_status rt_render_denoised_svgf_temporal(rt_ctx* c, const rt_camera* cam, cons
     return render_denoised(c, cam, proj, view, frame, seed, rr, dp, levels, sigma_luminance, out_rgba, out_color, alphas);
 }
 
+rt_status rt_render_denoised_svgf_clamped(rt_ctx* c, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame,
+                                          uint64_t seed, float rr, const rt_denoise_params* dp, int32_t levels, float sigma_luminance,
+                                          float alpha_color, float alpha_moments, float alpha_fast, float clamp_sigma, uint32_t* out_rgba,
+                                          float* out_color)
+{
+    if (!c) return RT_ERR_INVALID;
+    if (levels < 1 || levels > 8) { c->err = "a-trous levels must be in 1 .. 8"; return RT_ERR_INVALID; }
+    if (!(sigma_luminance > 0.0f) || !std::isfinite(sigma_luminance)) { c->err = "sigma_luminance must be finite and positive"; return RT_ERR_INVALID; }
+    const float alphas[3] = {alpha_color, alpha_moments, alpha_fast};
+    for (float a : alphas)
+        if (!(a > 0.0f && a <= 1.0f)) { c->err = "alpha_color, alpha_moments and alpha_fast must be in (0, 1]"; return RT_ERR_INVALID; }
+    if (!(clamp_sigma >= 0.0f) || !std::isfinite(clamp_sigma)) { c->err = "clamp_sigma must be finite and not negative"; return RT_ERR_INVALID; }
+    const float fast[2] = {alpha_fast, clamp_sigma};
+    return render_denoised(c, cam, proj, view, frame, seed, rr, dp, levels, sigma_luminance, out_rgba, out_color, alphas, fast);
+}
+
+rt_status rt_get_svgf_fast_history(rt_ctx* c, float* fast)
+{
+    if (!c) return RT_ERR_INVALID;
+    if (!c->dn_pixels || !c->svgfc_last) { c->err = "the last denoised frame was not an rt_render_denoised_svgf_clamped one"; return RT_ERR_STATE; }
+    HIPC(c, hipSetDevice(c->device));
+    if (fast) HIPC(c, hipMemcpyAsync(fast, c->d_svgf_fast[c->svgf_m_cur], c->dn_pixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+
 rt_status rt_get_svgf_history(rt_ctx* c, float* hist_color, float* moments, float* integrated)
 {
     if (!c) return RT_ERR_INVALID;
-    if (!c->dn_pixels || !c->svgft_last) { c->err = "the last denoised frame was not an rt_render_denoised_svgf_temporal one"; return RT_ERR_STATE; }
+    if (!c->dn_pixels || !c->svgft_last) { c->err = "the last denoised frame was not an rt_render_denoised_svgf_temporal or _clamped one"; return RT_ERR_STATE; }
     HIPC(c, hipSetDevice(c->device));
     const size_t n = c->dn_pixels * sizeof(float4);
     if (hist_color) HIPC(c, hipMemcpyAsync(hist_color, c->d_svgf_hist, n, hipMemcpyDeviceToHost, c->stream));

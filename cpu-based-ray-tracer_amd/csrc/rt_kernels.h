@@ -185,6 +185,10 @@ struct SvgfTemporalParams {
     int have_hist;
     float alpha_color, alpha_moments;
     float prev_proj[16], prev_view[16];   // the history's camera
+    // fast_next != nullptr: the fast-history clamp (rt_svgf_clamp.hip) -- stage R' in place of R, then stage K
+    const float4* fast_prev;  // F of the previous frame: (fast color, bits of the primitive id)
+    float4* fast_next;        // F' (never fast_prev)
+    float alpha_fast, clamp_sigma;
 };
 // T != nullptr (with D.svgf): the levels run on the accumulated color and the temporal variance; D.have_prev must be 0
 hipError_t rt_launch_denoise(const DenoiseParams& D, hipStream_t stream, const SvgfTemporalParams* T = nullptr);
@@ -195,6 +199,10 @@ hipError_t rt_launch_atrous(const DenoiseParams& D, hipStream_t stream);
 hipError_t rt_launch_svgf(const DenoiseParams& D, hipStream_t stream, const SvgfTemporalParams* T = nullptr);
 // stages R and V: svgf_reproject_kernel, svgf_variance_kernel -> T.integrated, T.m_next, D.var0 (called by rt_launch_svgf)
 hipError_t rt_launch_svgf_accumulate(const DenoiseParams& D, const SvgfTemporalParams& T, hipStream_t stream);
+// with T.fast_next (rt_svgf_clamp.hip; called by rt_launch_svgf_accumulate): stage R', svgf_reproject_fast_kernel ->
+// T.integrated, T.m_next, T.fast_next; stage K, svgf_clamp_kernel: T.integrated clamped in place by T.fast_next's 5 x 5 windows
+hipError_t rt_launch_svgf_reproject_fast(const DenoiseParams& D, const SvgfTemporalParams& T, hipStream_t stream);
+hipError_t rt_launch_svgf_clamp(const DenoiseParams& D, const SvgfTemporalParams& T, hipStream_t stream);
 
 // GPU BVH build (rt_lbvh.hip): a Karras LBVH in the traversal layout (rt_layout.h nodes / tris).
 // verts: 9 floats per triangle (a, b, c); recs: the triangle records (4 float4 per triangle); n >= 2.

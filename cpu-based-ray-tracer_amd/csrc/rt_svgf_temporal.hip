@@ -188,9 +188,16 @@ hipError_t rt_launch_svgf_accumulate(const DenoiseParams& D, const SvgfTemporalP
     A.ep = coef(D.sigma_position); A.en = coef(D.sigma_normal); A.ek = coef(D.sigma_coplanarity);
     for (int k = 0; k < 16; ++k) { A.prev_proj[k] = T.prev_proj[k]; A.prev_view[k] = T.prev_view[k]; }
     const uint32_t blocks = (uint32_t)((D.W + AT_BW - 1) / AT_BW) * (uint32_t)((D.H + AT_BH - 1) / AT_BH);
-    hipLaunchKernelGGL(svgf_reproject_kernel, dim3(blocks), dim3(256), 0, stream, A);
-    hipError_t e = hipGetLastError();
+    hipError_t e;
+    if (T.fast_next) {
+        e = rt_launch_svgf_reproject_fast(D, T, stream);   // stage R' of 5.10: the same C_int and M', and F'
+    } else {
+        hipLaunchKernelGGL(svgf_reproject_kernel, dim3(blocks), dim3(256), 0, stream, A);
+        e = hipGetLastError();
+    }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(svgf_variance_kernel, dim3(blocks), dim3(256), 0, stream, A);
-    return hipGetLastError();
+    e = hipGetLastError();
+    if (e != hipSuccess || !T.fast_next) return e;
+    return rt_launch_svgf_clamp(D, T, stream);   // stage K (it touches C_int alone: either order with stage V)
 }

@@ -24,6 +24,8 @@
  *   rt_render_denoised_svgf, rt_get_variance   (no reference counterpart: the a-trous pass guided by a luminance variance)
  *   rt_render_denoised_svgf_temporal, rt_get_svgf_history   (no reference counterpart: full SVGF, that pass behind a
  *                                         temporal accumulation of color and luminance moments)
+ *   rt_render_denoised_svgf_clamped, rt_get_svgf_fast_history   (no reference counterpart: full SVGF whose accumulated
+ *                                         color is clamped to a fast history's local statistics)
  *   rt_scene_add_world_sphere / _mesh     Whitted Style Ray Tracer Sphere / TriangleMesh + World::Add
  *                                         (WH/Sphere.h:16-75, WH/TriangleMesh.h:47-155, WH/World.h:37-45)
  *   rt_scene_add_two_spheres_scene        Whitted Style Ray Tracer Renderer::Renderer()       WH/Renderer.cpp:27-49
@@ -417,8 +419,25 @@ rt_status rt_render_denoised_svgf_temporal(rt_ctx* ctx, const rt_camera* cam, co
                                            float alpha_color, float alpha_moments, uint32_t* out_rgba, float* out_color);
 /* the state after the last rt_render_denoised_svgf_temporal frame (W x H x 4 floats each; any pointer may be NULL):
  * the color the next frame will reproject, the moments (mu1, mu2, history length, the primitive id as the bits of an
- * int32) and that frame's accumulated color.  RT_ERR_STATE when the last denoised frame was not of that kind. */
+ * int32) and that frame's accumulated color.  RT_ERR_STATE when the last denoised frame was neither of that kind nor
+ * an rt_render_denoised_svgf_clamped one. */
 rt_status rt_get_svgf_history(rt_ctx* ctx, float* hist_color, float* moments, float* integrated);
+/* full SVGF with a fast-history color clamp between the accumulation and the levels.  A second history
+ * accumulates the frame's color over the same reprojection with the weight max(alpha_fast, 1 / history length); per
+ * channel, the mean m and standard deviation s of its 5 x 5 neighbourhood (contributors inside the image) bound the
+ * accumulated color to [m - clamp_sigma s, m + clamp_sigma s] before the levels filter it, on every frame, the first
+ * included.  Moments, history length and variance are not touched by the clamp.  levels, sigma_luminance and the two
+ * alphas as in rt_render_denoised_svgf_temporal; alpha_fast in (0, 1]; clamp_sigma finite and >= 0.  The history is
+ * this entry point's own: rt_denoise_restart, a change of resolution or a denoised frame of any other kind, an
+ * rt_render_denoised_svgf_temporal one included, drops it, and a frame of this kind drops theirs.  rt_get_variance and
+ * rt_get_svgf_history work after such a frame (integrated is then the clamped color). */
+rt_status rt_render_denoised_svgf_clamped(rt_ctx* ctx, const rt_camera* cam, const float proj[16], const float view[16], uint32_t frame,
+                                          uint64_t seed, float rr, const rt_denoise_params* p, int32_t levels, float sigma_luminance,
+                                          float alpha_color, float alpha_moments, float alpha_fast, float clamp_sigma, uint32_t* out_rgba,
+                                          float* out_color);
+/* the fast history after the last rt_render_denoised_svgf_clamped frame (W x H x 4 floats): the fast color and the
+ * primitive id as the bits of an int32.  RT_ERR_STATE when the last denoised frame was not of that kind. */
+rt_status rt_get_svgf_fast_history(rt_ctx* ctx, float* fast);
 rt_status rt_denoise_restart(rt_ctx* ctx);
 /* the last denoised frame's buffers (W x H each; any pointer may be NULL): G-buffer color / world
  * position / normal (4 floats per pixel), primitive id (-1: primary ray missed), joint bilateral output */
